@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the gem_amd hot path (DESIGN.md "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload node2vec|gf|hope]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload node2vec|gf|hope] [--dump-outputs DIR] [--full]
 
-One JSON line on stdout (rank 0).  A "step" is one pass of the hot path over a synthetic graph
+One JSON line on stdout (rank 0).  A plain run does what the headline figure needs and nothing else: it builds the graph, runs W warm-up steps, times K
+steps, writes the outputs of the last step if --dump-outputs is given, and prints the line (`metric`, `value`, `unit`, `ms_per_step`, ...).  Everything else
+described below -- `roofline`, `quality`, `api_wall`, `cpu_baseline`, the other BASELINE configurations under "workloads", the detail record -- is measured
+only with --full.  A "step" is one pass of the hot path over a synthetic graph
 that is already resident in HBM when the timed region starts:
     node2vec  one full node2vec.learn_embedding on SBM(1M nodes, 10M edges): walks (r=10, l=80,
               p=q=1) + vocabulary + unigram table + SGNS (k=10, 5 negatives, 1 epoch), d=128.
               BASELINE.json quotes its metric on this graph (configs[3]); edges/sec =
               graph.number_of_edges() / wall of the pass.
     gf        one SGD sweep over all edges of the same SBM, d=128; edges/sec = edges x sweeps / wall.
-With no --workload the headline workload (node2vec) is timed first and the other two BASELINE configurations follow in the
+With no --workload the headline workload (node2vec) is timed; with --full the other two BASELINE configurations follow in the
 same process -- GF on SBM 10k/100k with examples/run_sbm.py:66's eta/lambda (configs[1]) and on the 1M/10M graph, HOPE on SBM
 100k/1M (configs[2]) -- each with its own timed region, roofline and cpu_baseline under "workloads" of the one JSON line.
 For N>1 either launch one rank per GPU with torch.distributed.run (what the driver does) or run plain `python bench.py --gpus N`, which
@@ -21,6 +24,14 @@ fixed => "scaling": "strong".
 `roofline`: for the dominant kernel, algorithmic bytes per launch (SURVEY 8d per-unit figure x units
 the launch processes) / average launch duration measured with HIP events on the launch stream.
 `cpu_baseline`: the reference CPU path timed on this box's host cores on a bounded sample.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed, float32 (integers: float64); a table above the size
+budget as a fixed sample of its rows (DUMP_SEED).  Graph, initial tables and seeds are fixed.
+    DIR/<name>.npy           arrays that are the same in every run, so two builds run with the same arguments compare output for output: gf `embedding`;
+                             hope `U`, `V`, `sigma`; node2vec `walks_head` (the head of the walk corpus) and `vocab_counts` (of the whole corpus)
+    DIR/hogwild/<name>.npy   node2vec `embedding`: the SynPos table a caller of the pass receives.  It is trained by a Hogwild launch, racy by design, so
+                             two runs of ONE build differ in it far beyond rounding (N2VWorkload.outputs); compare it statistically (`quality`)
+A plain run does not record HIP events around the SGNS launches, a --full run does (for `roofline`): two event records per launch inside the timed region.
 """
 import argparse
 import ctypes as C
@@ -41,6 +52,8 @@ import torch.distributed as dist
 from gem_amd import _hip, multi_gpu
 from gem_amd.graph import sbm_graph, edge_arrays, to_csr
 
+DUMP_BUDGET_BYTES = 48 << 20    # --dump-outputs: all files of one run together
+DUMP_SEED = 20260923
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable by a float4 copy)
 
 
@@ -63,6 +76,24 @@ def pmc_traffic(kernel, key):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(outputs, path, racy=()):
+    """--dump-outputs: {name: 1-d or 2-d array (torch or numpy)} -> path/<name>.npy, float32 (integer arrays: float64, exact); the names in `racy` (arrays
+    that are not reproducible from run to run) go to path/hogwild/<name>.npy, so that every file directly in `path` is.  The budget is split evenly over the arrays; one that does
+    not fit is written as a sorted sample of its rows, drawn without replacement from RandomState(DUMP_SEED): the same rows in every run."""
+    os.makedirs(os.path.join(path, 'hogwild') if racy else path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(outputs))
+    for name, a in sorted(outputs.items()):
+        dtype = np.float32 if (a.dtype.is_floating_point if torch.is_tensor(a) else a.dtype.kind == 'f') else np.float64
+        row_bytes = np.dtype(dtype).itemsize * (int(np.prod(a.shape[1:])) if len(a.shape) > 1 else 1)
+        if a.shape[0] * row_bytes > share:
+            rows = np.sort(np.random.RandomState(DUMP_SEED).choice(a.shape[0], size=share // row_bytes, replace=False))
+            a = a[torch.from_numpy(rows).to(a.device)] if torch.is_tensor(a) else a[rows]
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        f = os.path.join(path, 'hogwild', name + '.npy') if name in racy else os.path.join(path, name + '.npy')
+        np.save(f, np.ascontiguousarray(a, dtype=dtype))
+        log('dumped %s %s -> %s' % (name, a.shape, f))
 
 
 _GRAPHS = {}
@@ -145,6 +176,9 @@ class GFWorkload(object):
 
     def units_per_step(self):
         return self.n_edges
+
+    def outputs(self):
+        return {'embedding': self.last[:self.graph[0]]}
 
     def roofline(self, dev_ms_total, steps):
         launches = steps * self.b.levels
@@ -276,6 +310,8 @@ class GFWorkload(object):
 class N2VWorkload(object):
     metric, unit, dtype, kernel = 'edges/sec', 'edges/s', 'f32', 'sgns_win_kernel'
     default_steps, default_warmup = 2, 1
+    DUMP_WALKS = 16384         # --dump-outputs: the first walks of the corpus (x walk_len tokens; 10 MB as float64 at l = 80)
+    RACY_OUTPUTS = ('embedding',)
 
     def __init__(self, args, rank, world, comm):
         self.name = '%s%dk_%dk_node2vec_d%d_r%d_l%d_k%d' % (args.graph, args.nodes // 1000, args.edges // 1000, args.d, args.num_walks,
@@ -299,9 +335,10 @@ class N2VWorkload(object):
             self.job = multi_gpu.Node2VecPartitioned(self.b, comm, rank, world, n, args.num_walks, args.walk_len, args.window, 1,
                                                      seed=20260923, flags=_hip.N2V_SNAP_LAYOUT, episodes=args.episodes)
         self.sgns_ms, self.sgns_launches, self.pairs = 0.0, 0, 0
-        self._orig_train = self.b.train
-        self.b.train = self._timed_train
         self.evs = []
+        if getattr(args, 'full', False):          # `roofline` needs the SGNS launches' own HIP events
+            self._orig_train = self.b.train
+            self.b.train = self._timed_train
 
     def _timed_train(self, *a):
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
@@ -318,6 +355,17 @@ class N2VWorkload(object):
 
     def units_per_step(self):
         return self.n_edges
+
+    def outputs(self):
+        """`embedding`: the SynPos table the pass returns.  It is trained by a Hogwild launch -- wavefronts update shared rows without locks, by design, as
+        the reference's threads do -- so two runs of one build differ in it far beyond rounding (two passes at SBM 1M/10M: 18 % in the Frobenius norm, the
+        MAP within 0.2-0.3 %: tests/README.md); RACY_OUTPUTS keeps it apart from the part of a pass that is the same in every run: the first DUMP_WALKS
+        walks of this rank's shard and the vocabulary counts (how often each node occurs in the whole corpus)."""
+        k = min(self.DUMP_WALKS, self.job.hi - self.job.lo)
+        walks = torch.empty((k, self.args.walk_len), dtype=torch.int32, device=self.P.device)
+        _hip.check(_hip.lib().gemhip_n2v_copy_walks(self.b.h, 0, k, C.c_void_p(walks.data_ptr()), None))
+        torch.cuda.synchronize()
+        return {'embedding': self.P, 'walks_head': walks, 'vocab_counts': self.b.counts}
 
     def phase_split(self, steps):
         ph = self.job.phase_seconds() if hasattr(self.job, 'phase_seconds') else None
@@ -610,6 +658,9 @@ class HopeWorkload(object):
     def units_per_step(self):
         return self.n * self.world
 
+    def outputs(self):
+        return {'U': self.dU, 'V': self.dV, 'sigma': self.sig}
+
     def host_output_seconds(self, reps=3):
         """The numpy-out form (gemhip_hope_plan_solve: what HOPE.learn_embedding calls), wall seconds per solve, outside the timed region."""
         st = (C.c_double * 12)()
@@ -750,24 +801,26 @@ def capi_multi(args, rank, world):
                 secs.append(st[0] + st[1])
         el = float(np.sum(secs))
         assert np.isfinite(X).all()
-        from gem_amd.evaluation import reconstruction as gr
-        nodes = np.random.RandomState(0).choice(n, size=min(1024, n), replace=False)
-        ap = gr.sampled_ap_gpu(g, None, X, nodes)
         out.update({'value': g.number_of_edges() * K / el, 'ms_per_step': el * 1e3 / K,
                     'config': {'workload': '%s%dk_%dk_node2vec_d%d_r%d_l%d_k%d' % (args.graph, args.nodes // 1000, args.edges // 1000, args.d, args.num_walks, args.walk_len, args.window),
                                'nodes': n, 'directed_edges': g.number_of_edges(), 'd': args.d, 'sharding': 'start-node x%d, partitioned tables' % N,
                                'driver': 'capi gemhip_n2v_train_multi' + (' (virtual ranks on one GPU)' if virt else '')},
                     'phases': {'walks_vocab_gather_s': st[0], 'train_s': st[1], 'pairs_trained': st[3], 'ring_shift_bytes_per_rank_per_round': st[4],
-                               'bucket_launches_per_rank': st[7], 'virtual_ranks': st[6]},
-                    'quality': {'sampled_map': float(ap.mean()), 'nodes_sampled': int(len(nodes)),
-                                'unigram_layout': 'vocabulary order per partition (GEMHIP_N2V_VOCAB_ORDER: the plugin default)'}})
+                               'bucket_launches_per_rank': st[7], 'virtual_ranks': st[6]}})
+        if args.full:
+            from gem_amd.evaluation import reconstruction as gr
+            nodes = np.random.RandomState(0).choice(n, size=min(1024, n), replace=False)
+            ap = gr.sampled_ap_gpu(g, None, X, nodes)
+            out['quality'] = {'sampled_map': float(ap.mean()), 'nodes_sampled': int(len(nodes)),
+                              'unigram_layout': 'vocabulary order per partition (GEMHIP_N2V_VOCAB_ORDER: the plugin default)'}
     out['config']['world_size_seen'] = world
     out['call_wall_s_incl_uploads_and_planning'] = time.perf_counter() - t_all
     return out
 
 
-def time_workload(name, args, rank, world, comm, K=None, W=None, with_cpu=True):
-    """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.
+def time_workload(name, args, rank, world, comm, K=None, W=None, with_cpu=True, dump_dir=None):
+    """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.  `dump_dir`: rank 0 writes the
+    outputs of the last timed step there (--dump-outputs).  Only with args.full: `roofline`, `quality`, `api_wall`, `cpu_baseline`.
     Returns (result dict on rank 0 else None, workload)."""
     wl = WORKLOADS[name](args, rank, world, comm)
     K = K if K is not None else wl.default_steps
@@ -803,6 +856,8 @@ def time_workload(name, args, rank, world, comm, K=None, W=None, with_cpu=True):
     el = float(t.item())
     if rank != 0:
         return None, wl
+    if dump_dir:
+        dump_outputs(wl.outputs(), dump_dir, getattr(wl, 'RACY_OUTPUTS', ()))
     out = {
         'metric': wl.metric, 'value': wl.units_per_step() * K / el, 'unit': wl.unit, 'n_gpus': world, 'steps': K, 'warmup': W,
         'ms_per_step': el * 1e3 / K, 'higher_is_better': True,
@@ -815,6 +870,8 @@ def time_workload(name, args, rank, world, comm, K=None, W=None, with_cpu=True):
         out['config']['world_size_seen'] = dist.get_world_size()
         if hasattr(wl, 'phase_split'):
             out['phases'] = wl.phase_split(K)
+    if not args.full:
+        return out, wl
     if world == 1:
         out['roofline'] = wl.roofline(dev_ms, K)          # (before quality(): that may run one more, untimed pass on the same handle)
     if hasattr(wl, 'quality'):
@@ -910,8 +967,12 @@ def compact_line(full, detail_path=None):
     return s
 
 
-def emit(full):
-    """Rank 0: the detail record (everything measured, tens of KB) to a file and to stderr; then the compact line -- the only line on stdout."""
+def emit(full, detail=True):
+    """Rank 0: the detail record (everything measured, tens of KB) to a file and to stderr; then the compact line -- the only line on stdout.
+    A plain run (detail=False) has measured nothing beyond the line and prints the line alone."""
+    if not detail:
+        print(compact_line(full), flush=True)
+        return
     detail_path = None
     text = json.dumps(full)
     for d in (os.environ.get('GEM_BENCH_DETAIL_DIR'), os.path.join(ROOT, 'gpurun_out'), tempfile.gettempdir()):
@@ -956,10 +1017,16 @@ def main():
     ap.add_argument('--driver', default='torch', choices=['torch', 'capi'], help="N>1: 'torch' = one process per GPU over torch.distributed (gem_amd/multi_gpu.py, "
                     "what the driver's command launches); 'capi' = rank 0 calls the library's own N-GPU entry points (gemhip_*_train_multi: one process, n_gpus devices)")
     ap.add_argument('--virtual-ranks', action='store_true', help='--driver capi: run the N ranks as virtual ranks on device 0 (the one-GPU test box)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-api-wall', action='store_true', help='skip the extra learn_embedding() pass that fills `api_wall` (outside the timed region)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32; a table '
+                    'above the size budget as a fixed, seeded sample of its rows)')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline figure does not need: roofline, quality (MAP against the committed reference '
+                    'runs), api_wall, cpu_baseline, and with no --workload every other BASELINE configuration; writes the detail record')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip `cpu_baseline`')
+    ap.add_argument('--no-api-wall', action='store_true', help='--full: skip the extra learn_embedding() pass that fills `api_wall` (outside the timed region)')
     args = ap.parse_args()
 
+    if args.dump_outputs and args.driver == 'capi':
+        raise SystemExit('bench.py --dump-outputs: not with --driver capi (the one-shot entry points hand back the final table only)')
     if not torch.cuda.is_available():
         raise SystemExit('bench.py needs an MI355X: torch.cuda.is_available() is False (there is no CPU fallback)')
     if args.gpus > 1 and args.driver == 'capi' and 'WORLD_SIZE' not in os.environ:
@@ -968,7 +1035,7 @@ def main():
             raise SystemExit('bench.py --gpus %d --driver capi: only %d GPU(s) visible (--virtual-ranks runs them on device 0)' % (args.gpus, torch.cuda.device_count()))
         torch.cuda.set_device(0)
         _hip.check(_hip.lib().gemhip_set_device(0))
-        emit(capi_multi(args, 0, 1))
+        emit(capi_multi(args, 0, 1), args.full)
         return
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- N ranks of this very command under torch.distributed.run, one per GPU
@@ -1005,16 +1072,16 @@ def main():
             dist.barrier()
         out = capi_multi(args, rank, world)
         if rank == 0:
-            emit(out)
+            emit(out, args.full)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
         return
     comm = multi_gpu.TorchComm(world)
     headline = 'node2vec' if args.workload == 'all' else args.workload
-    out, wl = time_workload(headline, args, rank, world, comm, args.steps, args.warmup, with_cpu=not args.no_cpu_baseline)
+    out, wl = time_workload(headline, args, rank, world, comm, args.steps, args.warmup, with_cpu=not args.no_cpu_baseline, dump_dir=args.dump_outputs)
 
-    if args.workload == 'all' and world == 1 and (args.nodes, args.edges, args.graph) == (1000000, 10000000, 'sbm'):
+    if args.full and args.workload == 'all' and world == 1 and (args.nodes, args.edges, args.graph) == (1000000, 10000000, 'sbm'):
         # the other two BASELINE configurations, each with its own timed region (their step counts are their own defaults)
         del wl
         torch.cuda.empty_cache()
@@ -1065,7 +1132,7 @@ def main():
         out['workloads'] = extra
 
     if rank == 0:
-        emit(out)
+        emit(out, args.full)
     if world > 1:
         dist.barrier()                       # rank 0 scores the embedding after the timed region: nobody tears the group down under it
         dist.destroy_process_group()

@@ -2,7 +2,7 @@
 
 The prebuilt SNAP ELF (gem/c_exe/node2vec, copied to oracle/_ref/node2vec by oracle/Makefile) seeds its generators with time(NULL).
 Under oracle/_ref/libfaketime.so (oracle/shim/faketime.c: time() pinned to $GEM_FAKE_TIME) and OMP_NUM_THREADS=1 it is
-deterministic.  It has no option to print its walks, so it runs under the debugger (rocgdb ships with ROCm), stops where
+deterministic.  It has no option to print its walks, so it runs under a host debugger ($GDB; any gdb-compatible one), stops where
 node2vec() hands the finished walk matrix to LearnEmbeddings() (0x40ea30; first argument TVVec<TInt,int64>& = {XDim, YDim, {MxVals,
 Vals, ValT*}}) and the matrix is dumped from memory.  Graph files are written the way gem/utils/graph_util.py:137-140
 (saveGraphToEdgeListTxtn2v) writes them and the flags are those of gem/embedding/node2vec.py:35-46 (-dr -w).
@@ -20,7 +20,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 REF = os.path.join(ROOT, 'oracle', '_ref')
-GDB = '/opt/rocm/bin/rocgdb'
+GDB = os.environ.get('GDB', 'gdb')
 
 
 def edge_lines(kind):
@@ -80,7 +80,7 @@ CASES = [
 
 def main():
     out = {'_how': 'scripts/make_golden_n2v_snap_stream.py: gem/c_exe/node2vec under oracle/shim/faketime.c (GEM_FAKE_TIME = seed), OMP_NUM_THREADS=1, '
-                   'walk matrix dumped with rocgdb at LearnEmbeddings() entry; flags -dr -w as gem/embedding/node2vec.py:35-46', 'cases': {}}
+                   'walk matrix dumped with a host debugger at LearnEmbeddings() entry; flags -dr -w as gem/embedding/node2vec.py:35-46', 'cases': {}}
     for name, graph, p, q, r, l, seed, (d, window, epochs) in CASES:
         lines = edge_lines(graph)
         walks, emb = run_binary(lines, d, l, r, window, p, q, seed, epochs)

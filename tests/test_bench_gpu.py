@@ -36,7 +36,7 @@ def test_two_rank_bench_line(launcher, workload, extra):
         env.pop(k, None)
     head = [sys.executable] if launcher == 'self' else [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                                                          '--master-addr', '127.0.0.1', '--master-port', str(_free_port())]
-    cmd = head + [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', workload,
+    cmd = head + [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--workload', workload, '--full',          # (--full: `quality` and the detail record)
                   '--nodes', '16384', '--edges', '163840', '--blocks', '8'] + extra
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -72,12 +72,12 @@ def _stdout_line(r):
 
 
 def test_single_gpu_stdout_is_one_short_line_with_roofline_and_cpu_baseline(tmp_path):
-    """`python bench.py` (one workload, small graph): exactly one stdout line, < 4 KB, carrying `roofline` and `cpu_baseline` with their contract
+    """`python bench.py --full` (one workload, small graph): exactly one stdout line, < 4 KB, carrying `roofline` and `cpu_baseline` with their contract
     fields; everything else (notes, API wall, the full objects) is in the detail record on stderr and in the file the line names."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
     env['GEM_BENCH_DETAIL_DIR'] = str(tmp_path)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'gf', '--nodes', '16384', '--edges', '163840', '--blocks', '8',
-                        '--steps', '20', '--warmup', '2'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        '--steps', '20', '--warmup', '2', '--full'], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _stdout_line(r)
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data', 'config',
@@ -96,6 +96,69 @@ def test_single_gpu_stdout_is_one_short_line_with_roofline_and_cpu_baseline(tmp_
     assert json.load(open(os.path.join(str(tmp_path), 'bench_detail_latest.json')))['value'] == full['value']
 
 
+def _plain_run(workload, extra, out):
+    """One plain `bench.py --gpus 1` of `workload` on the small graph with --dump-outputs `out`: (the stdout line, {file name: array})."""
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    env['GEM_BENCH_DETAIL_DIR'] = os.path.join(out, 'detail')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--workload', workload, '--nodes', '16384', '--edges', '163840',
+                        '--blocks', '8', '--dump-outputs', out] + extra, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert 'BENCH_DETAIL' not in r.stderr and not os.path.exists(os.path.join(out, 'detail'))
+    return _stdout_line(r), {f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out)) if f.endswith('.npy')}
+
+
+@pytest.mark.parametrize('workload,extra,names', [('gf', ['--steps', '7', '--warmup', '2'], ['embedding']),
+                                                  ('node2vec', ['--steps', '1', '--warmup', '1'], ['vocab_counts', 'walks_head']),
+                                                  ('hope', ['--steps', '2', '--warmup', '1'], ['U', 'V', 'sigma'])])
+def test_plain_run_prints_the_headline_line_alone_and_dumps_reproducible_outputs(workload, extra, names, tmp_path):
+    """Without --full the run times its steps and prints the line: no `roofline`, `cpu_baseline`, `quality`, `api_wall`, no detail record.  --dump-outputs
+    writes the last step's outputs as .npy files (float32, integer arrays as float64), within the size budget, and two runs with the same arguments write
+    the same arrays directly into the directory: GF's and HOPE's outputs, node2vec's walks and vocabulary counts.  node2vec's table is trained by a Hogwild
+    launch: it is written under hogwild/ and checked for what two racy launches share -- shape, the sampled rows, finite and trained values."""
+    runs = []
+    for tag in ('a', 'b'):
+        j, arrays = _plain_run(workload, extra, str(tmp_path / tag))
+        for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'dtype', 'config'):
+            assert k in j, k
+        for k in ('roofline', 'cpu_baseline', 'quality', 'api_wall', 'workloads', 'detail'):
+            assert k not in j, k
+        assert j['steps'] == int(extra[1]) and j['warmup'] == int(extra[3]) and j['ms_per_step'] > 0 and j['higher_is_better'] is True
+        units = 16384 if workload == 'hope' else j['config']['directed_edges']
+        assert j['value'] == pytest.approx(units / (j['ms_per_step'] * 1e-3), rel=1e-6)
+        assert sorted(arrays) == sorted(names)
+        assert sorted(os.listdir(str(tmp_path / tag))) == sorted([n + '.npy' for n in names] + (['hogwild'] if workload == 'node2vec' else []))
+        runs.append(arrays)
+    for n in names:
+        a, b = runs[0][n], runs[1][n]
+        assert a.dtype == (np.float64 if workload == 'node2vec' else np.float32) and a.shape == b.shape and a.shape[0] > 0 and np.isfinite(a).all() and np.abs(a).max() > 0
+        assert np.array_equal(a, b), n
+    total = sum(a.nbytes for a in runs[0].values())
+    if workload == 'gf':
+        assert runs[0]['embedding'].shape == (16384, 128)
+    elif workload == 'node2vec':
+        w, c = runs[0]['walks_head'], runs[0]['vocab_counts']
+        assert w.shape == (16384, 80) and c.shape == (16384,) and 0 < c.sum() <= 80 * 10 * 16384 and np.array_equal(w, np.round(w))
+        assert w.min() >= -1 and w.max() < 16384 and np.all(c[w[:, 0].astype(np.int64)] > 0)
+        tabs = [np.load(str(tmp_path / tag / 'hogwild' / 'embedding.npy')) for tag in ('a', 'b')]
+        assert os.listdir(str(tmp_path / 'a' / 'hogwild')) == ['embedding.npy']
+        for t in tabs:
+            # sgns_init draws SynPos uniformly from (-0.5 / d, 0.5 / d) (word2vec's InitPosEmb): a row above that has been trained
+            assert t.dtype == np.float32 and t.shape == (16384, 128) and np.isfinite(t).all()
+            assert np.all(np.abs(t[c > 0]).max(axis=1) > 0.5 / 128)
+        total += tabs[0].nbytes
+    else:
+        assert runs[0]['U'].shape == runs[0]['V'].shape == (16384, 64) and runs[0]['sigma'].shape == (64,)
+    assert total <= 64e6
+
+
+def test_steps_and_warmup_set_the_number_of_gf_sweeps(tmp_path):
+    """--steps counted on the OUTPUT, not on what the line says about itself: GF's table after W warm-up and K timed steps is W + K sweeps of the same
+    initial table (deterministic), so 2 + 7 and 4 + 5 give the same bits and 2 + 6 does not."""
+    tab = {kw: _plain_run('gf', ['--steps', str(kw[0]), '--warmup', str(kw[1])], str(tmp_path / ('k%d_w%d' % kw)))[1]['embedding'] for kw in ((7, 2), (5, 4), (6, 2))}
+    assert np.array_equal(tab[7, 2], tab[5, 4])
+    assert not np.array_equal(tab[7, 2], tab[6, 2])
+
+
 @pytest.mark.parametrize('workload,launcher', [('gf', 'self'), ('node2vec', 'self'), ('gf', 'torchrun')])
 def test_capi_driver_times_the_librarys_own_n_gpu_entry_points(workload, launcher):
     """`bench.py --gpus 2 --driver capi --virtual-ranks`: the line comes from gemhip_gf_train_multi / gemhip_n2v_train_multi (one process, the ranks
@@ -105,7 +168,7 @@ def test_capi_driver_times_the_librarys_own_n_gpu_entry_points(workload, launche
         env.pop(k, None)
     head = [sys.executable] if launcher == 'self' else [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                                                          '--master-addr', '127.0.0.1', '--master-port', str(_free_port())]
-    extra = ['--steps', '4', '--warmup', '1'] if workload == 'gf' else ['--steps', '1', '--warmup', '0', '--episodes', '4']
+    extra = ['--steps', '4', '--warmup', '1'] if workload == 'gf' else ['--steps', '1', '--warmup', '0', '--episodes', '4', '--full']      # (`quality`)
     r = subprocess.run(head + [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--driver', 'capi', '--virtual-ranks', '--workload', workload, '--nodes', '16384',
                                '--edges', '163840', '--blocks', '8'] + extra, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -73,15 +73,13 @@ n2v.node2vec.learn_embedding = _n2v
 '''
 
 
-def test_reference_run_karate_runs_unchanged_against_the_alias_package(tmp_path):
-    if not os.path.exists(REF_SCRIPT):
-        pytest.skip('reference tree not present on this box')
+def _run_and_check(cmd, tmp_path):
     os.makedirs(tmp_path / 'data')
     shutil.copyfile(golden_path('karate.edgelist'), tmp_path / 'data' / 'karate.edgelist')
     (tmp_path / 'site').mkdir()
     (tmp_path / 'site' / 'sitecustomize.py').write_text(STAND_IN)
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([str(tmp_path / 'site'), ROOT, os.environ.get('PYTHONPATH', '')]), MPLBACKEND='Agg')
-    r = subprocess.run([sys.executable, REF_SCRIPT, '-node2vec', '1'], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable] + cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=900)
     out = r.stdout
     blocks = re.findall(r'(\w+):\n\tTraining time: ([\d.]+)\n\tMAP: ([\d.eE+-]+) ', out)
     names = [b[0] for b in blocks]
@@ -90,3 +88,15 @@ def test_reference_run_karate_runs_unchanged_against_the_alias_package(tmp_path)
     assert r.returncode != 0 and 'SDNE is out of scope' in r.stderr          # ... and refused to train (out of scope: SURVEY section 2)
     maps = {b[0]: float(b[2]) for b in blocks}
     assert all(0.0 < v < 1.0 for v in maps.values()), maps
+
+
+def test_reference_run_karate_runs_unchanged_against_the_alias_package(tmp_path):
+    if not os.path.exists(REF_SCRIPT):
+        pytest.skip('reference tree not present on this box')
+    _run_and_check([REF_SCRIPT, '-node2vec', '1'], tmp_path)
+
+
+def test_own_run_karate_driver_runs_against_the_alias_package(tmp_path):
+    """The same sequence and assertions through this repository's own driver of that flow (examples/run_karate_hip.py: same models, hyper-parameters and
+    output format, SDNE last): needs no reference tree, so it runs everywhere.  It shows that OUR driver runs, not that the reference's script does."""
+    _run_and_check([os.path.join(ROOT, 'examples', 'run_karate_hip.py'), '-node2vec', '1', '-sdne', '1'], tmp_path)
