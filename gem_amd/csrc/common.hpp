@@ -40,6 +40,57 @@ struct PhaseScope {
     ~PhaseScope() { phase_acc()[k] += phase_now() - t0; }
 };
 
+// ---------------------------------------------------------------- owned memory
+// The one owner of device (DevBuf) and pinned host (PinnedBuf) memory in this library: move-only, frees in its destructor on the device it
+// allocated on.  Converts to T* for kernel arguments and copies.  Memory the library only borrows from a caller stays a plain T* view.
+template <typename T, bool PINNED>
+class Buf {
+    T *p_ = nullptr; size_t cap_ = 0; int dev_ = 0;
+    void release(bool wait)       // free on the block's own device, then back to the caller's (if the current device cannot be read: on whichever is current)
+    {
+        if (!p_) return;
+        int cur = dev_;
+        const bool hop = hipGetDevice(&cur) == hipSuccess && cur != dev_;
+        if (hop) (void)hipSetDevice(dev_);
+        if (wait) (void)hipDeviceSynchronize();          // (a failure here is not lost: the free below synchronises too, and the next call reports it)
+        (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+        if (hop) (void)hipSetDevice(cur);
+        p_ = nullptr; cap_ = 0;
+    }
+public:
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    Buf(Buf &&o) noexcept : p_(o.p_), cap_(o.cap_), dev_(o.dev_) { o.p_ = nullptr; o.cap_ = 0; }
+    Buf &operator=(Buf &&o) noexcept { if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; dev_ = o.dev_; o.p_ = nullptr; o.cap_ = 0; } return *this; }
+    ~Buf() { reset(); }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t capacity() const { return cap_; }          // elements asked for by the reserve() that allocated the block
+    void reset() { release(false); }
+    // Grow-only, contents NOT preserved.  Holding a block of >= count elements: no HIP call at all.  Otherwise: wait for the block's device (a launch
+    // in flight may still read the old block), free it, allocate at least 16 bytes on the current device (so an empty buffer's reserve(0) still
+    // yields a valid pointer: empty graphs).  On failure the buffer is empty.
+    hipError_t reserve(size_t count)
+    {
+        if (p_ && count <= cap_) return hipSuccess;
+        release(true);
+        const size_t bytes = count * sizeof(T) > 16 ? count * sizeof(T) : 16;
+        hipError_t e = hipGetDevice(&dev_);
+        if (e == hipSuccess) e = PINNED ? hipHostMalloc((void **)&p_, bytes, hipHostMallocDefault) : hipMalloc((void **)&p_, bytes);
+        if (e != hipSuccess) { p_ = nullptr; return e; }
+        cap_ = count;
+        return hipSuccess;
+    }
+    hipError_t upload(const T *host, size_t count)     // reserve + blocking copy from pageable or pinned host memory
+    {
+        const hipError_t e = reserve(count);
+        return e != hipSuccess || !count ? e : hipMemcpy(p_, host, count * sizeof(T), hipMemcpyHostToDevice);
+    }
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinnedBuf = Buf<T, true>;
+
 constexpr int WAVE = 64;          // CDNA wavefront
 constexpr int NUM_XCD = 8;        // MI355X: 8 XCDs, block b lands on XCD b % 8
 

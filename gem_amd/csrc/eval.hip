@@ -126,27 +126,23 @@ extern "C" int gemhip_eval_sampled_ap(int64_t n, int32_t da, int32_t ld, const f
     const int64_t nchunk = (int64_t)chunk_node.size(), total = (int64_t)nb.size();
     std::vector<double> s_host(std::max<int64_t>(total, 1)); std::vector<int32_t> cnt_host(std::max<int64_t>(total, 1));
     if (nchunk > 0) {
-        float *dA = nullptr, *dB = nullptr; int32_t *dnb = nullptr, *dcn = nullptr, *dcc = nullptr, *dcnt = nullptr; int64_t *dco = nullptr; double *ds = nullptr;
-        auto cleanup = [&]() { hipFree(dA); if (dB != dA) hipFree(dB); hipFree(dnb); hipFree(dcn); hipFree(dcc); hipFree(dco); hipFree(dcnt); hipFree(ds); };
-#define EV_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) { cleanup(); return fail(GEMHIP_E_HIP, "eval_sampled_ap: %s: %s", #x, hipGetErrorString(_e)); } } while (0)
-        const size_t mat = (size_t)n * ld * sizeof(float);
-        EV_TRY(hipMalloc((void **)&dA, mat)); EV_TRY(hipMemcpy(dA, A_host, mat, hipMemcpyHostToDevice));
-        if (B_host && B_host != A_host) { EV_TRY(hipMalloc((void **)&dB, mat)); EV_TRY(hipMemcpy(dB, B_host, mat, hipMemcpyHostToDevice)); } else dB = dA;
-        EV_TRY(hipMalloc((void **)&dnb, total * 4)); EV_TRY(hipMemcpy(dnb, nb.data(), total * 4, hipMemcpyHostToDevice));
-        EV_TRY(hipMalloc((void **)&dcn, nchunk * 4)); EV_TRY(hipMemcpy(dcn, chunk_node.data(), nchunk * 4, hipMemcpyHostToDevice));
-        EV_TRY(hipMalloc((void **)&dcc, nchunk * 4)); EV_TRY(hipMemcpy(dcc, chunk_cnt.data(), nchunk * 4, hipMemcpyHostToDevice));
-        EV_TRY(hipMalloc((void **)&dco, nchunk * 8)); EV_TRY(hipMemcpy(dco, chunk_off.data(), nchunk * 8, hipMemcpyHostToDevice));
-        EV_TRY(hipMalloc((void **)&ds, total * 8)); EV_TRY(hipMalloc((void **)&dcnt, total * 4));
+        DevBuf<float> bufA, bufB; DevBuf<int32_t> dnb, dcn, dcc, dcnt; DevBuf<int64_t> dco; DevBuf<double> ds;
+        GEMHIP_CHECK(bufA.upload(A_host, (size_t)n * ld));
+        if (B_host && B_host != A_host) GEMHIP_CHECK(bufB.upload(B_host, (size_t)n * ld));
+        const float *dA = bufA, *dB = bufB ? bufB.get() : bufA.get();
+        GEMHIP_CHECK(dnb.upload(nb.data(), total));
+        GEMHIP_CHECK(dcn.upload(chunk_node.data(), nchunk));
+        GEMHIP_CHECK(dcc.upload(chunk_cnt.data(), nchunk));
+        GEMHIP_CHECK(dco.upload(chunk_off.data(), nchunk));
+        GEMHIP_CHECK(ds.reserve(total)); GEMHIP_CHECK(dcnt.reserve(total));
         const int nv = (da + WAVE - 1) / WAVE;
 #define EV_LAUNCH(NV) hipLaunchKernelGGL((eval_ap_kernel<NV>), dim3((unsigned)nchunk), dim3(EV_BLOCK), 0, 0, n, (int)da, dA, dB, (int)ld, (int)undirected, \
-                                         dcn, dco, dcc, dnb, ds, dcnt)
+                                         dcn.get(), dco.get(), dcc.get(), dnb.get(), ds.get(), dcnt.get())
         if (nv <= 1) EV_LAUNCH(1); else if (nv <= 2) EV_LAUNCH(2); else if (nv <= 4) EV_LAUNCH(4); else EV_LAUNCH(8);
 #undef EV_LAUNCH
-        EV_TRY(hipGetLastError());
-        EV_TRY(hipMemcpy(s_host.data(), ds, total * 8, hipMemcpyDeviceToHost));
-        EV_TRY(hipMemcpy(cnt_host.data(), dcnt, total * 4, hipMemcpyDeviceToHost));
-#undef EV_TRY
-        cleanup();
+        GEMHIP_CHECK(hipGetLastError());
+        GEMHIP_CHECK(hipMemcpy(s_host.data(), ds, total * 8, hipMemcpyDeviceToHost));
+        GEMHIP_CHECK(hipMemcpy(cnt_host.data(), dcnt, total * 4, hipMemcpyDeviceToHost));
     }
     // ---- AP_i = mean over true neighbours with s > 0 of rank_hit / rank_all ; rank_hit = position among the neighbours in
     //      the evaluator's order (score descending, node id ascending on ties), rank_all = 1 + the streamed count

@@ -40,12 +40,12 @@ struct gemhip_gf_plan {
     std::vector<int64_t> level_hubs;  // ... of which the first level_hubs[L] are hub rows (gf_hub_kernel)
     std::vector<int64_t> level_maxlen;  // longest non-hub row of the level, in firing edges (the rows-per-wavefront rule looks at it)
     hipStream_t hub_stream = nullptr; hipEvent_t hub_fork = nullptr, hub_join = nullptr;
-    int32_t *d_rows = nullptr;        // row ids in processing order (sorted by level, then reference order)
-    int64_t *d_ptr = nullptr;         // CSR offsets over d_rows
-    uint32_t *d_col = nullptr;        // neighbour id | (1u<<31 if that neighbour is read from X_new)
-    float *d_w = nullptr;
-    float *X[2] = {nullptr, nullptr};
-    bool own_X = false;
+    DevBuf<int32_t> d_rows;           // row ids in processing order (sorted by level, then reference order)
+    DevBuf<int64_t> d_ptr;            // CSR offsets over d_rows
+    DevBuf<uint32_t> d_col;           // neighbour id | (1u<<31 if that neighbour is read from X_new)
+    DevBuf<float> d_w;
+    float *X[2] = {nullptr, nullptr};   // the two tables the kernels ping-pong between: X_own's blocks, or the caller's (gemhip_gf_plan_bind)
+    DevBuf<float> X_own[2];             // empty while the tables are borrowed
     int cur = 0;                      // X[cur] holds the latest table
     int rows_per_wave = 0;            // 0 = auto (gf_rows_per_wave), else forced (gemhip_gf_plan_set_rows_per_wave: tests, A/B)
     // sweeps per cooperative launch (gf_sweeps_coop_kernel): 0 = off (one launch per sweep and level), k > 1 = up to k sweeps per launch on single-level
@@ -695,15 +695,10 @@ extern "C" int gemhip_gf_plan_create(int64_t n, int64_t m, const int32_t *src, c
     if (hipGetDevice(&p->device) != hipSuccess) { delete p; return fail(GEMHIP_E_HIP, "gf_plan_create: no HIP device"); }
     phase_acc()[PH_HOST] += phase_now() - t_host0;
     PhaseScope ph_up(PH_H2D);
-    auto up = [&](void **dp, const void *hp, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dp, bytes ? bytes : 16);
-        if (e != hipSuccess) return e;
-        return bytes ? hipMemcpy(*dp, hp, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    };
-    hipError_t e = up((void **)&p->d_rows, rows_sorted.data(), nrows * sizeof(int32_t));
-    if (e == hipSuccess) e = up((void **)&p->d_ptr, ptr_sorted.data(), (nrows + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = up((void **)&p->d_col, col_sorted.data(), nupd * sizeof(uint32_t));
-    if (e == hipSuccess) e = up((void **)&p->d_w, w_sorted.data(), nupd * sizeof(float));
+    hipError_t e = p->d_rows.upload(rows_sorted.data(), nrows);
+    if (e == hipSuccess) e = p->d_ptr.upload(ptr_sorted.data(), nrows + 1);
+    if (e == hipSuccess) e = p->d_col.upload(col_sorted.data(), nupd);
+    if (e == hipSuccess) e = p->d_w.upload(w_sorted.data(), nupd);
     if (e != hipSuccess) {
         gemhip_gf_plan_destroy(p);
         return fail(GEMHIP_E_HIP, "gf_plan_create: device upload failed: %s", hipGetErrorString(e));
@@ -715,9 +710,7 @@ extern "C" int gemhip_gf_plan_create(int64_t n, int64_t m, const int32_t *src, c
 extern "C" int gemhip_gf_plan_destroy(gemhip_gf_plan_t p)
 {
     if (!p) return GEMHIP_OK;
-    hipFree(p->d_rows); hipFree(p->d_ptr); hipFree(p->d_col); hipFree(p->d_w);
     if (p->hub_stream) { hipStreamSynchronize(p->hub_stream); hipStreamDestroy(p->hub_stream); hipEventDestroy(p->hub_fork); hipEventDestroy(p->hub_join); }
-    if (p->own_X) { hipFree(p->X[0]); hipFree(p->X[1]); }
     delete p;
     return GEMHIP_OK;
 }
@@ -725,18 +718,15 @@ extern "C" int gemhip_gf_plan_destroy(gemhip_gf_plan_t p)
 static int ensure_tables(gemhip_gf_plan_t p)
 {
     if (p->X[0]) return GEMHIP_OK;
-    const size_t bytes = (size_t)p->n * p->d * sizeof(float);
-    GEMHIP_CHECK(hipMalloc((void **)&p->X[0], bytes));
-    GEMHIP_CHECK(hipMalloc((void **)&p->X[1], bytes));
-    p->own_X = true;
-    p->cur = 0;
+    for (int k = 0; k < 2; ++k) GEMHIP_CHECK(p->X_own[k].reserve((size_t)p->n * p->d));
+    p->X[0] = p->X_own[0]; p->X[1] = p->X_own[1]; p->cur = 0;
     return GEMHIP_OK;
 }
 
 extern "C" int gemhip_gf_plan_bind(gemhip_gf_plan_t p, void *dXa, void *dXb)
 {
     GEMHIP_REQUIRE(p && dXa && dXb && dXa != dXb, "gf_plan_bind: need two distinct device buffers");
-    if (p->own_X) { hipFree(p->X[0]); hipFree(p->X[1]); p->own_X = false; }
+    p->X_own[0].reset(); p->X_own[1].reset();
     p->X[0] = (float *)dXa; p->X[1] = (float *)dXb; p->cur = 0;
     return GEMHIP_OK;
 }
@@ -895,26 +885,15 @@ extern "C" int gemhip_gf_objective(int64_t n, int64_t m, const int32_t *src, con
                                    const float *X_host, double *out)
 {
     GEMHIP_REQUIRE(n > 0 && m >= 0 && d >= 1 && X_host && out, "gf_objective: bad arguments");
-    int32_t *ds = nullptr, *dd = nullptr; float *dw = nullptr, *dX = nullptr; double *dout = nullptr;
-    int rc = GEMHIP_OK;
-    auto cleanup = [&]() { hipFree(ds); hipFree(dd); hipFree(dw); hipFree(dX); hipFree(dout); };
-#define OBJ_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) { cleanup(); return fail(GEMHIP_E_HIP, "gf_objective: %s: %s", #x, hipGetErrorString(_e)); } } while (0)
-    OBJ_TRY(hipMalloc((void **)&ds, std::max<int64_t>(m, 1) * 4));
-    OBJ_TRY(hipMalloc((void **)&dd, std::max<int64_t>(m, 1) * 4));
-    if (w) OBJ_TRY(hipMalloc((void **)&dw, std::max<int64_t>(m, 1) * 4));
-    OBJ_TRY(hipMalloc((void **)&dX, (size_t)n * d * 4));
-    OBJ_TRY(hipMalloc((void **)&dout, 16));
-    if (m) {
-        OBJ_TRY(hipMemcpy(ds, src, m * 4, hipMemcpyHostToDevice));
-        OBJ_TRY(hipMemcpy(dd, dst, m * 4, hipMemcpyHostToDevice));
-        if (w) OBJ_TRY(hipMemcpy(dw, w, m * 4, hipMemcpyHostToDevice));
-    }
-    OBJ_TRY(hipMemcpy(dX, X_host, (size_t)n * d * 4, hipMemcpyHostToDevice));
-    OBJ_TRY(hipMemset(dout, 0, 16));
+    DevBuf<int32_t> ds, dd; DevBuf<float> dw, dX; DevBuf<double> dout;
+    GEMHIP_CHECK(ds.upload(src, m));
+    GEMHIP_CHECK(dd.upload(dst, m));
+    if (w) GEMHIP_CHECK(dw.upload(w, m));
+    GEMHIP_CHECK(dX.upload(X_host, (size_t)n * d));
+    GEMHIP_CHECK(dout.reserve(2));
+    GEMHIP_CHECK(hipMemset(dout, 0, 16));
     hipLaunchKernelGGL(gf_objective_kernel, dim3(2048), dim3(256), 0, 0, ds, dd, dw, dX, m, n, (int)d, dout);
-    OBJ_TRY(hipGetLastError());
-    OBJ_TRY(hipMemcpy(out, dout, 16, hipMemcpyDeviceToHost));
-#undef OBJ_TRY
-    cleanup();
-    return rc;
+    GEMHIP_CHECK(hipGetLastError());
+    GEMHIP_CHECK(hipMemcpy(out, dout, 16, hipMemcpyDeviceToHost));
+    return GEMHIP_OK;
 }

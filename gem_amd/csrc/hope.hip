@@ -1185,30 +1185,27 @@ struct Hope {
     float beta = 0.f;
     int mode = 0;                                    // 0: S = Katz (HOPE); 1: S = I + D^-1/2 A D^-1/2 (Laplacian Eigenmaps);
                                                      // 2: S = c I - (I-P)^T (I-P), P = D^-1 A (LLE), c in `beta`
-    int64_t *rp = nullptr, *rpT = nullptr;
-    int32_t *ci = nullptr, *ciT = nullptr;
-    float *va = nullptr, *vaT = nullptr;
-    float *P = nullptr; size_t P_bytes = 0;          // Gram slab partials
-    double *G = nullptr; size_t G_elems = 0;         // device fp64 Gram
-    double *G2 = nullptr; size_t G2_elems = 0;       // a second one (gram2: two Gram matrices, one host round trip)
-    double *Gpart = nullptr; size_t Gpart_elems = 0; // reduction scratch
-    float *Csmall = nullptr; size_t C_elems = 0;     // device small matrix for tsgemm
+    DevBuf<int64_t> rp, rpT;
+    DevBuf<int32_t> ci, ciT;
+    DevBuf<float> va, vaT;
+    DevBuf<float> P;                                 // Gram slab partials (colmax carves other types out of it: sized in bytes / 4)
+    DevBuf<double> G;                                // device fp64 Gram
+    DevBuf<double> G2;                               // a second one (gram2: two Gram matrices, one host round trip)
+    DevBuf<double> Gpart;                            // reduction scratch
+    DevBuf<float> Csmall;                            // device small matrix for tsgemm
     hipStream_t s = nullptr;
     double spmm_count = 0, spmm_cols = 0, eig_seconds = 0, eig_calls = 0;   // statistics
     hipEvent_t sp0 = nullptr, sp1 = nullptr; double spmm_ms = 0; bool time_spmm = false;
     std::vector<hipEvent_t> sp_pool; size_t sp_used = 0;      // (start, stop) pairs around SpMM runs; read once at the end of a solve
-    struct CoefSlot { float *h = nullptr, *d = nullptr; size_t elems = 0; hipEvent_t done = nullptr; };
+    struct CoefSlot { PinnedBuf<float> h; DevBuf<float> d; hipEvent_t done = nullptr; };
     CoefSlot coef[8]; unsigned coef_next = 0;                // pinned staging ring for the small host matrices tsgemm() takes
-    float *ws[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; size_t ws_elems[7] = {0, 0, 0, 0, 0, 0, 0};   // eigen-path workspace, kept across solves
-    float *d_cm = nullptr;                                   // 512 floats: column arg-max signs of the output step
+    DevBuf<float> ws[7];                                     // eigen-path workspace, kept across solves
+    DevBuf<float> d_cm;                                      // 512 floats: column arg-max signs of the output step
     int err = 0;
-    ~Hope()
+    ~Hope()          // the events; the buffers free themselves
     {
-        hipFree(rp); hipFree(rpT); hipFree(ci); hipFree(ciT); hipFree(va); hipFree(vaT); hipFree(P); hipFree(G); hipFree(G2); hipFree(Gpart); hipFree(Csmall);
         for (hipEvent_t e : sp_pool) hipEventDestroy(e);
-        for (CoefSlot &c : coef) { if (c.h) hipHostFree(c.h); hipFree(c.d); if (c.done) hipEventDestroy(c.done); }
-        for (float *w : ws) hipFree(w);
-        hipFree(d_cm);
+        for (CoefSlot &c : coef) if (c.done) hipEventDestroy(c.done);
     }
 };
 
@@ -1265,15 +1262,15 @@ static void gram_launch(Hope &H, const float *X, int ldx, int m1, const float *Y
     rows_per_slab = (rows_per_slab + 7) / 8 * 8;
     const int nslabs = (int)((H.n + rows_per_slab - 1) / rows_per_slab);
     const size_t need = (size_t)nslabs * m1p * m2p * sizeof(float);
-    if (need > H.P_bytes) { hipFree(H.P); H.P = nullptr; H.P_bytes = 0; HOPE_TRY(H, hipMalloc((void **)&H.P, need)); if (!H.err) H.P_bytes = need; }
-    double *&Gd = second ? H.G2 : H.G; size_t &Gd_elems = second ? H.G2_elems : H.G_elems;
-    if ((size_t)m1 * m2 > Gd_elems) { hipFree(Gd); Gd = nullptr; Gd_elems = 0; HOPE_TRY(H, hipMalloc((void **)&Gd, (size_t)m1 * m2 * sizeof(double))); if (!H.err) Gd_elems = (size_t)m1 * m2; }
+    HOPE_TRY(H, H.P.reserve(need / sizeof(float)));
+    DevBuf<double> &Gd = second ? H.G2 : H.G;
+    HOPE_TRY(H, Gd.reserve((size_t)m1 * m2));
     if (H.err) return;
     const int ntiles = t1 * t2;
     hipLaunchKernelGGL(hope_gram_kernel, dim3((ntiles + 3) / 4, nslabs), dim3(256), 0, H.s, H.n, X, ldx, m1, Y, ldy, m2, rows_per_slab, t2, ntiles,
                        H.P, m1p, m2p);
     const int Cr = std::min(nslabs, 64);
-    if ((size_t)Cr * m1 * m2 > H.Gpart_elems) { hipFree(H.Gpart); H.Gpart = nullptr; H.Gpart_elems = 0; HOPE_TRY(H, hipMalloc((void **)&H.Gpart, (size_t)Cr * m1 * m2 * sizeof(double))); if (!H.err) H.Gpart_elems = (size_t)Cr * m1 * m2; }
+    HOPE_TRY(H, H.Gpart.reserve((size_t)Cr * m1 * m2));
     if (H.err) return;
     hipLaunchKernelGGL(hope_reduce1_kernel, dim3((m1 * m2 + 255) / 256, Cr), dim3(256), 0, H.s, H.P, nslabs, (int64_t)m1p * m2p, m1, m2, m2p, Cr, H.Gpart);
     hipLaunchKernelGGL(hope_reduce2_kernel, dim3((m1 * m2 + 255) / 256), dim3(256), 0, H.s, H.Gpart, Cr, m1 * m2, Gd, Gf);
@@ -1312,23 +1309,24 @@ void gram2(Hope &H, const float *Xa, int ldxa, int ma1, const float *Ya, int ldy
     HOPE_TRY(H, hipStreamSynchronize(H.s));
 }
 
+// The small host matrices of tsgemm() / ritz_rotate() go through a ring of pinned host / device slot pairs: no host synchronisation between the
+// upload and the launch.  The next slot, holding >= need floats on both sides, once the launch that last read it (eight calls ago) has finished.
+static Hope::CoefSlot &coef_slot(Hope &H, size_t need)
+{
+    Hope::CoefSlot &slot = H.coef[H.coef_next++ % 8];
+    if (slot.done) HOPE_TRY(H, hipEventSynchronize(slot.done));
+    else HOPE_TRY(H, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    const size_t cap = std::max<size_t>(need, 16384);
+    HOPE_TRY(H, slot.h.reserve(cap));
+    HOPE_TRY(H, slot.d.reserve(cap));
+    return slot;
+}
+
 // Out[:, :b2] = (Src ? Src : 0) + alpha * X[:, :m] * C   (C host fp64 m x b2 row-major)
 void tsgemm(Hope &H, const float *X, int ldx, int m, const std::vector<double> &Ch, int b2, float alpha, const float *Src, int lds_, float *Out, int ldo)
 {
     if (H.err || b2 == 0) return;
-    // the coefficients go through a ring of pinned host / device slot pairs: no host synchronisation between the upload and the launch
-    Hope::CoefSlot &slot = H.coef[H.coef_next++ % 8];
-    const size_t need = (size_t)std::max(m, 1) * b2;
-    if (slot.done) HOPE_TRY(H, hipEventSynchronize(slot.done));          // the launch that last read this slot (eight tsgemm calls ago)
-    else HOPE_TRY(H, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    if (need > slot.elems && !H.err) {
-        if (slot.h) hipHostFree(slot.h);
-        hipFree(slot.d); slot.h = nullptr; slot.d = nullptr; slot.elems = 0;
-        const size_t cap = std::max<size_t>(need, 16384);
-        HOPE_TRY(H, hipHostMalloc((void **)&slot.h, cap * sizeof(float), hipHostMallocDefault));
-        HOPE_TRY(H, hipMalloc((void **)&slot.d, cap * sizeof(float)));
-        if (!H.err) slot.elems = cap;
-    }
+    Hope::CoefSlot &slot = coef_slot(H, (size_t)std::max(m, 1) * b2);
     if (H.err) return;
     for (size_t i = 0; i < (size_t)m * b2; ++i) slot.h[i] = (float)Ch[i];
     HOPE_TRY(H, hipMemcpyAsync(slot.d, slot.h, (size_t)m * b2 * sizeof(float), hipMemcpyHostToDevice, H.s));
@@ -1343,23 +1341,13 @@ void ritz_rotate(Hope &H, const float *V, int ldv, const float *B, int ldb, int 
 {
     res2.assign(b2, 0.0);
     if (H.err || b2 == 0 || m == 0) return;
-    Hope::CoefSlot &slot = H.coef[H.coef_next++ % 8];
     const size_t need = (size_t)m * b2 + b2;
-    if (slot.done) HOPE_TRY(H, hipEventSynchronize(slot.done));
-    else HOPE_TRY(H, hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    if (need > slot.elems && !H.err) {
-        if (slot.h) hipHostFree(slot.h);
-        hipFree(slot.d); slot.h = nullptr; slot.d = nullptr; slot.elems = 0;
-        const size_t cap = std::max<size_t>(need, 16384);
-        HOPE_TRY(H, hipHostMalloc((void **)&slot.h, cap * sizeof(float), hipHostMallocDefault));
-        HOPE_TRY(H, hipMalloc((void **)&slot.d, cap * sizeof(float)));
-        if (!H.err) slot.elems = cap;
-    }
+    Hope::CoefSlot &slot = coef_slot(H, need);
     const int ct = (b2 + 31) / 32, b2p = ct * 32;
     const int64_t ntr = (H.n + 31) / 32;
     const size_t pneed = (size_t)ntr * b2p * sizeof(float);
-    if (pneed > H.P_bytes && !H.err) { HOPE_TRY(H, hipStreamSynchronize(H.s)); hipFree(H.P); H.P = nullptr; H.P_bytes = 0; HOPE_TRY(H, hipMalloc((void **)&H.P, pneed)); if (!H.err) H.P_bytes = pneed; }
-    if ((size_t)b2 > H.G_elems && !H.err) { HOPE_TRY(H, hipStreamSynchronize(H.s)); hipFree(H.G); H.G = nullptr; H.G_elems = 0; HOPE_TRY(H, hipMalloc((void **)&H.G, (size_t)b2 * sizeof(double))); if (!H.err) H.G_elems = (size_t)b2; }
+    HOPE_TRY(H, H.P.reserve(pneed / sizeof(float)));
+    HOPE_TRY(H, H.G.reserve(b2));
     if (H.err) return;
     for (size_t i = 0; i < (size_t)m * b2; ++i) slot.h[i] = (float)Ch[i];
     for (int j = 0; j < b2; ++j) slot.h[(size_t)m * b2 + j] = (float)theta[j];
@@ -1383,9 +1371,9 @@ void colmax(Hope &H, const float *X, int ld, int mc, float *val)
     const int64_t rows_per_chunk = (H.n + nchunks - 1) / nchunks;
     const size_t per = (size_t)nchunks * mc;
     const size_t need = per * (sizeof(float) * 2 + sizeof(long long)) + 64;
-    if (need > H.P_bytes) { HOPE_TRY(H, hipStreamSynchronize(H.s)); hipFree(H.P); H.P = nullptr; H.P_bytes = 0; HOPE_TRY(H, hipMalloc((void **)&H.P, need)); if (!H.err) H.P_bytes = need; }
+    HOPE_TRY(H, H.P.reserve((need + 3) / sizeof(float)));
     if (H.err) return;
-    long long *pidx = reinterpret_cast<long long *>(H.P);                    // (8-byte aligned part first)
+    long long *pidx = reinterpret_cast<long long *>(H.P.get());                    // (8-byte aligned part first)
     float *pabs = reinterpret_cast<float *>(pidx + per), *pval = pabs + per;
     hipLaunchKernelGGL(hope_colmax1_kernel, dim3(nchunks, (mc + 63) / 64), dim3(256), 0, H.s, H.n, X, ld, mc, rows_per_chunk, pabs, pval, pidx);
     hipLaunchKernelGGL(hope_colmax2_kernel, dim3(mc), dim3(256), 0, H.s, nchunks, mc, pabs, pval, pidx, val);
@@ -1397,7 +1385,7 @@ void project_out(Hope &H, const float *V, int ldv, int m, float *W, int ldw, int
 {
     if (H.err || m == 0 || cols == 0) return;
     const size_t need = (size_t)m * cols;
-    if (need > H.C_elems) { HOPE_TRY(H, hipStreamSynchronize(H.s)); hipFree(H.Csmall); H.Csmall = nullptr; H.C_elems = 0; HOPE_TRY(H, hipMalloc((void **)&H.Csmall, need * sizeof(float))); if (!H.err) H.C_elems = need; }
+    HOPE_TRY(H, H.Csmall.reserve(need));
     if (H.err) return;
     gram_launch(H, V, ldv, m, W, ldw, cols, H.Csmall);
     if (H.err) return;
@@ -1560,13 +1548,11 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
     const int mmax = (int)std::min<int64_t>(std::min<int64_t>(basis_cols, n), 512);
     GEMHIP_REQUIRE(b <= 512 && k <= mmax, "hope: k + oversample = %d too large (max 512)", b);
     const int ldm = (mmax + 31) / 32 * 32, ldb = (b + 31) / 32 * 32;
-    float *Vall = nullptr, *Ball = nullptr, *T0 = nullptr, *T1 = nullptr, *W0 = nullptr, *Tmp = nullptr;
-    auto dalloc = [&](float **p, size_t cols) { HOPE_TRY(H, hipMalloc((void **)p, (size_t)n * cols * sizeof(float))); if (!H.err) HOPE_TRY(H, hipMemset(*p, 0, (size_t)n * cols * sizeof(float))); };
-    dalloc(&Vall, ldm); dalloc(&Ball, ldm); dalloc(&T0, ldb); dalloc(&T1, ldb); dalloc(&W0, ldb); dalloc(&Tmp, ldm);
+    DevBuf<float> Vall, Ball, T0, T1, W0, Tmp;
+    auto dalloc = [&](DevBuf<float> &p, size_t cols) { HOPE_TRY(H, p.reserve((size_t)n * cols)); HOPE_TRY(H, hipMemset(p, 0, (size_t)n * cols * sizeof(float))); };
+    dalloc(Vall, ldm); dalloc(Ball, ldm); dalloc(T0, ldb); dalloc(T1, ldb); dalloc(W0, ldb); dalloc(Tmp, ldm);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto cleanup = [&]() {          // also on the error paths: buffers and the four timing events
-        hipFree(Vall); hipFree(Ball); hipFree(T0); hipFree(T1); hipFree(W0); hipFree(Tmp);
-        Vall = Ball = T0 = T1 = W0 = Tmp = nullptr;
+    auto drop_events = [&]() {      // also on the error paths: the four timing events
         if (ev0) hipEventDestroy(ev0);
         if (ev1) hipEventDestroy(ev1);
         if (H.sp0) hipEventDestroy(H.sp0);
@@ -1574,7 +1560,7 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
         ev0 = ev1 = nullptr; H.sp0 = H.sp1 = nullptr;
     };
     if (!H.err) { HOPE_TRY(H, hipEventCreate(&ev0)); HOPE_TRY(H, hipEventCreate(&ev1)); HOPE_TRY(H, hipEventCreate(&H.sp0)); HOPE_TRY(H, hipEventCreate(&H.sp1)); H.time_spmm = (stats != nullptr); }
-    if (H.err) { cleanup(); return H.err; }
+    if (H.err) { drop_events(); return H.err; }
     hipEventRecord(ev0, H.s);
 
     const int64_t threads = (n * (int64_t)b + 3) / 4;
@@ -1674,7 +1660,7 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
         if (H.err) break;
         mt = std::min(ma, b);                                       // restart block and output never use more than b Ritz pairs
         sym_eig_top(ma, Wv, mt, ev, Zt);
-        GEMHIP_REQUIRE(mc >= k || (cleanup(), false), "hope: Krylov space collapsed to %d < k=%d columns (rank-deficient S?)", mc, k);
+        GEMHIP_REQUIRE(mc >= k || (drop_events(), false), "hope: Krylov space collapsed to %d < k=%d columns (rank-deficient S?)", mc, k);
         {
             std::vector<double> all(lock_sig);
             for (int j = 0; j < std::min(mt, k); ++j) all.push_back(std::sqrt(std::max(ev[j], 0.0)));
@@ -1727,7 +1713,7 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
         // deterministic sign: largest-magnitude entry of each left vector positive (svds signs are arbitrary; the first such row on ties).  The
         // arg-maxima are taken on the device from the compact [n][k] product, the signs go into the coefficients and the product is formed again
         // (one more 36 us GEMM; rounds 1-2 flipped the n x k outputs in two host passes -- ~10 ms at 100k x 64, and impossible for device outputs)
-        if (!H.d_cm) HOPE_TRY(H, hipMalloc((void **)&H.d_cm, 512 * sizeof(float)));       // kept in the plan: no hipMalloc / hipFree (a device sync) per solve
+        HOPE_TRY(H, H.d_cm.reserve(512));       // kept in the plan: no hipMalloc / hipFree (a device sync) per solve
         float *d_cm = H.d_cm;
         const std::vector<double> &Cref = U_sqrtS ? Cu : Cv;
         if (!H.err) tsgemm(H, U_sqrtS ? Ball : Vall, ldm, mc, Cref, k, 1.0f, nullptr, 0, Tmp, k);           // compact [n][k]
@@ -1757,7 +1743,7 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
         stats[0] = ms * 1e-3; stats[1] = H.spmm_count; stats[2] = H.spmm_cols; stats[3] = terms; stats[4] = mc; stats[5] = restarts_done;
         stats[6] = last_change; stats[7] = br; stats[8] = g_eig_seconds; stats[9] = g_eig_calls; stats[10] = last_residual; stats[11] = H.spmm_ms * 1e-3;
     }
-    cleanup();
+    drop_events();
     return H.err;
 }
 
@@ -1883,20 +1869,18 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
     // workspace: seven n x ldv blocks kept in the solver state across solves (a plan is solved repeatedly; hipMalloc / hipFree of
     // ~40 MB blocks cost more than a filter cycle)
     auto walloc = [&](int slot, float **p, size_t elems) {
-        if (elems > H.ws_elems[slot] && !H.err) {
-            hipFree(H.ws[slot]); H.ws[slot] = nullptr; H.ws_elems[slot] = 0;
-            HOPE_TRY(H, hipMalloc((void **)&H.ws[slot], elems * sizeof(float)));
-            if (!H.err) H.ws_elems[slot] = elems;
+        if (elems > H.ws[slot].capacity() && !H.err) {
+            HOPE_TRY(H, H.ws[slot].reserve(elems));
             // zeroed when allocated: the padding columns (b .. ldv) are never written and never read as data, but they must not hold NaN patterns for
             // the tools that scan whole buffers; a reused block holds the finite values of the previous solve (seven memsets per solve saved)
-            if (!H.err) HOPE_TRY(H, hipMemsetAsync(H.ws[slot], 0, elems * sizeof(float), H.s));
+            HOPE_TRY(H, hipMemsetAsync(H.ws[slot], 0, elems * sizeof(float), H.s));
         }
         *p = H.ws[slot];
     };
     walloc(0, &Vall, (size_t)n * ldv); walloc(1, &Bm, (size_t)n * ldv); walloc(2, &F[0], (size_t)n * ldv); walloc(3, &F[1], (size_t)n * ldv);
     walloc(4, &F[2], (size_t)n * ldv); walloc(5, &Tmp, (size_t)n * ldv); walloc(6, &colv, 512);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    auto cleanup = [&]() {
+    auto drop_events = [&]() {
         if (ev0) hipEventDestroy(ev0);
         if (ev1) hipEventDestroy(ev1);
         if (H.sp0) hipEventDestroy(H.sp0);
@@ -1904,7 +1888,7 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
         ev0 = ev1 = nullptr; H.sp0 = H.sp1 = nullptr;
     };
     if (!H.err) { HOPE_TRY(H, hipEventCreate(&ev0)); HOPE_TRY(H, hipEventCreate(&ev1)); HOPE_TRY(H, hipEventCreate(&H.sp0)); HOPE_TRY(H, hipEventCreate(&H.sp1)); H.time_spmm = (stats != nullptr); }
-    if (H.err) { cleanup(); return H.err; }
+    if (H.err) { drop_events(); return H.err; }
     hipEventRecord(ev0, H.s);
     const auto ht1 = std::chrono::steady_clock::now();
 
@@ -2092,7 +2076,7 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
             if (lo > -1e-6 * L) lo = -1e-6 * L;
         }
     }
-    if (!H.err && !converged) { *fell_back = true; cleanup(); return GEMHIP_OK; }
+    if (!H.err && !converged) { *fell_back = true; drop_events(); return GEMHIP_OK; }
     const auto ht2 = std::chrono::steady_clock::now();
     if (!H.err) {
         struct Cand { double s, lam; int col; };
@@ -2139,7 +2123,7 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
         stats[11] = H.spmm_ms * 1e-3;
     }
     (void)degree_total;
-    cleanup();
+    drop_events();
     return H.err;
 }
 
@@ -2201,9 +2185,8 @@ static int hope_setup(gemhip_hope_plan &P, int64_t n, int64_t nnz, const int64_t
     }
     int devid = 0;
     if (hipGetDevice(&devid) != hipSuccess) return fail(GEMHIP_E_HIP, "hope: no HIP device");
-    auto up = [&](void **dp, const void *hp, size_t bytes) { HOPE_TRY(H, hipMalloc(dp, std::max<size_t>(bytes, 16))); if (!H.err && bytes) HOPE_TRY(H, hipMemcpy(*dp, hp, bytes, hipMemcpyHostToDevice)); };
-    up((void **)&H.rp, row_ptr, (n + 1) * sizeof(int64_t)); up((void **)&H.ci, col, nnz * sizeof(int32_t)); up((void **)&H.va, va.data(), nnz * sizeof(float));
-    up((void **)&H.rpT, rpT.data(), (n + 1) * sizeof(int64_t)); up((void **)&H.ciT, ciT.data(), nnz * sizeof(int32_t)); up((void **)&H.vaT, vaT.data(), nnz * sizeof(float));
+    HOPE_TRY(H, H.rp.upload(row_ptr, n + 1)); HOPE_TRY(H, H.ci.upload(col, nnz)); HOPE_TRY(H, H.va.upload(va.data(), nnz));
+    HOPE_TRY(H, H.rpT.upload(rpT.data(), n + 1)); HOPE_TRY(H, H.ciT.upload(ciT.data(), nnz)); HOPE_TRY(H, H.vaT.upload(vaT.data(), nnz));
     if (H.err) return H.err;
 
     double rho = 0.0;
@@ -2211,9 +2194,9 @@ static int hope_setup(gemhip_hope_plan &P, int64_t n, int64_t nnz, const int64_t
         // hence the margin.  X2 = [x | z] as an n x 2 block so that one Gram launch returns both norms.
         std::vector<float> x0((size_t)n * 2, 0.f);
         for (int64_t i = 0; i < n; ++i) x0[(size_t)i * 2] = (float)(1.0 + 0.37 * std::sin(12.9898 * (double)(i + 1)));
-        float *X2 = nullptr, *yv = nullptr;
-        up((void **)&X2, x0.data(), x0.size() * sizeof(float));
-        HOPE_TRY(H, hipMalloc((void **)&yv, (size_t)n * sizeof(float)));
+        DevBuf<float> X2, yv;
+        HOPE_TRY(H, X2.upload(x0.data(), x0.size()));
+        HOPE_TRY(H, yv.reserve(n));
         for (int it = 0; it < 40 && !H.err; ++it) {
             spmm(H, false, 1.0f, X2, 2, nullptr, 0, yv, 1, 1);                       // y = A x
             spmm(H, true, 1.0f, yv, 1, nullptr, 0, X2 + 1, 2, 1);                    // z = A^T y
@@ -2229,7 +2212,6 @@ static int hope_setup(gemhip_hope_plan &P, int64_t n, int64_t nnz, const int64_t
             if (it >= 4 && std::fabs(rho - prev) <= 1e-3 * rho) break;                // the 10 % margin below covers the rest
         }
         HOPE_TRY(H, hipStreamSynchronize(H.s));
-        hipFree(X2); hipFree(yv);
         if (H.err) return H.err;
         rho = std::min(std::max(rho * 1.1, 1e-30), std::sqrt(rs_max * cs_max));
     }
@@ -2357,11 +2339,11 @@ static int svd_error_impl(gemhip_hope_plan_t P, int32_t k, const float *sigma, c
     for (int j = 0; j < k; ++j) GEMHIP_REQUIRE(std::isfinite(sigma[j]), "hope_plan_svd_error: sigma[%d] = %g", j, (double)sigma[j]);
     for (int64_t i = 0; i < n; ++i)
         for (int j = 0; j < k; ++j) Vh[(size_t)i * ldv + j] = sigma[j] > 0.f ? V_sqrtS[(size_t)i * k + j] / std::sqrt(sigma[j]) : 0.f;      // (a zero column deflates nothing)
-    float *dV = nullptr, *dBV = nullptr;
-    float *blk[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};          // Z (deflated in place), T0, T1, W0 (= B Z after apply_S), Out (= S Z)
-    HOPE_TRY(H, hipMalloc((void **)&dV, Vh.size() * sizeof(float)));
-    HOPE_TRY(H, hipMalloc((void **)&dBV, Vh.size() * sizeof(float)));
-    for (float *&b : blk) { HOPE_TRY(H, hipMalloc((void **)&b, (size_t)n * ld * sizeof(float))); if (!H.err) HOPE_TRY(H, hipMemsetAsync(b, 0, (size_t)n * ld * sizeof(float), H.s)); }
+    DevBuf<float> dV, dBV;
+    DevBuf<float> blk[5];                                                    // Z (deflated in place), T0, T1, W0 (= B Z after apply_S), Out (= S Z)
+    HOPE_TRY(H, dV.reserve(Vh.size()));
+    HOPE_TRY(H, dBV.reserve(Vh.size()));
+    for (DevBuf<float> &b : blk) { HOPE_TRY(H, b.reserve((size_t)n * ld)); HOPE_TRY(H, hipMemsetAsync(b, 0, (size_t)n * ld * sizeof(float), H.s)); }
     HOPE_TRY(H, hipMemcpyAsync(dV, Vh.data(), Vh.size() * sizeof(float), hipMemcpyHostToDevice, H.s));
     HOPE_TRY(H, hipMemsetAsync(dBV, 0, Vh.size() * sizeof(float), H.s));
     std::vector<double> Gbv, C, Gs, Gb;
@@ -2382,8 +2364,8 @@ static int svd_error_impl(gemhip_hope_plan_t P, int32_t k, const float *sigma, c
     double uside = 0.0;
     if (U_sqrtS && !H.err) {
         const int ldc = 128;
-        float *cb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // T0, T1, W0, Out (= S V chunk), U Sigma chunk / residual
-        for (float *&b : cb) HOPE_TRY(H, hipMalloc((void **)&b, (size_t)n * ldc * sizeof(float)));
+        DevBuf<float> cb[5];                                               // T0, T1, W0, Out (= S V chunk), U Sigma chunk / residual
+        for (DevBuf<float> &b : cb) HOPE_TRY(H, b.reserve((size_t)n * ldc));
         std::vector<float> Uh((size_t)n * ldc);
         for (int c0 = 0; c0 < k && !H.err; c0 += ldc) {
             const int cbn = std::min(ldc, k - c0);
@@ -2402,11 +2384,8 @@ static int svd_error_impl(gemhip_hope_plan_t P, int32_t k, const float *sigma, c
             HOPE_TRY(H, hipStreamSynchronize(H.s));
             if (!H.err) for (int j = 0; j < cbn; ++j) uside += Gr[(size_t)j * cpad + j];
         }
-        for (float *b : cb) hipFree(b);
     }
     HOPE_TRY(H, hipStreamSynchronize(H.s));
-    for (float *b : blk) hipFree(b);
-    hipFree(dV); hipFree(dBV);
     if (H.err) return H.err;
     double rem = 0.0, bv2 = 0.0, top = 0.0;
     for (int j = 0; j < probes; ++j) rem += Gs[(size_t)j * probes + j] - Gb[(size_t)j * probes + j];
@@ -2486,8 +2465,7 @@ extern "C" int gemhip_lap_eigmap(int64_t n, int64_t nnz, const int64_t *row_ptr,
         for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) va[e] = (float)(dinv[i] * (w ? w[e] : 1.0) * dinv[col[e]]);
     int devid = 0;
     if (hipGetDevice(&devid) != hipSuccess) return fail(GEMHIP_E_HIP, "lap_eigmap: no HIP device");
-    auto up = [&](void **dp, const void *hp, size_t bytes) { HOPE_TRY(H, hipMalloc(dp, std::max<size_t>(bytes, 16))); if (!H.err && bytes) HOPE_TRY(H, hipMemcpy(*dp, hp, bytes, hipMemcpyHostToDevice)); };
-    up((void **)&H.rp, row_ptr, (n + 1) * sizeof(int64_t)); up((void **)&H.ci, col, nnz * sizeof(int32_t)); up((void **)&H.va, va.data(), nnz * sizeof(float));
+    HOPE_TRY(H, H.rp.upload(row_ptr, n + 1)); HOPE_TRY(H, H.ci.upload(col, nnz)); HOPE_TRY(H, H.va.upload(va.data(), nnz));
     if (H.err) return H.err;
     std::vector<float> sig(k);
     // large graphs: the Chebyshev-filtered eigen-path of HOPE (the operator is one SpMM with a symmetric matrix); same switch
@@ -2547,9 +2525,8 @@ extern "C" int gemhip_lle(int64_t n, int64_t nnz, const int64_t *row_ptr, const 
     }
     int devid = 0;
     if (hipGetDevice(&devid) != hipSuccess) return fail(GEMHIP_E_HIP, "lle: no HIP device");
-    auto up = [&](void **dp, const void *hp, size_t bytes) { HOPE_TRY(H, hipMalloc(dp, std::max<size_t>(bytes, 16))); if (!H.err && bytes) HOPE_TRY(H, hipMemcpy(*dp, hp, bytes, hipMemcpyHostToDevice)); };
-    up((void **)&H.rp, row_ptr, (n + 1) * sizeof(int64_t)); up((void **)&H.ci, col, nnz * sizeof(int32_t)); up((void **)&H.va, va.data(), nnz * sizeof(float));
-    up((void **)&H.rpT, rpT.data(), (n + 1) * sizeof(int64_t)); up((void **)&H.ciT, ciT.data(), nnz * sizeof(int32_t)); up((void **)&H.vaT, vaT.data(), nnz * sizeof(float));
+    HOPE_TRY(H, H.rp.upload(row_ptr, n + 1)); HOPE_TRY(H, H.ci.upload(col, nnz)); HOPE_TRY(H, H.va.upload(va.data(), nnz));
+    HOPE_TRY(H, H.rpT.upload(rpT.data(), n + 1)); HOPE_TRY(H, H.ciT.upload(ciT.data(), nnz)); HOPE_TRY(H, H.vaT.upload(vaT.data(), nnz));
     if (H.err) return H.err;
     // c >= sigma_max(I - P)^2: power iteration on N^T N with the one-column SpMM (X2 = [x | z] so that one Gram launch gives both norms),
     // with a margin
@@ -2557,9 +2534,9 @@ extern "C" int gemhip_lle(int64_t n, int64_t nnz, const int64_t *row_ptr, const 
     {
         std::vector<float> x0((size_t)n * 2, 0.f);
         for (int64_t i = 0; i < n; ++i) x0[(size_t)i * 2] = (float)(1.0 + 0.61 * std::sin(7.31 * (double)(i + 1)));
-        float *X2 = nullptr, *tv = nullptr;
-        up((void **)&X2, x0.data(), x0.size() * sizeof(float));
-        HOPE_TRY(H, hipMalloc((void **)&tv, (size_t)n * sizeof(float)));
+        DevBuf<float> X2, tv;
+        HOPE_TRY(H, X2.upload(x0.data(), x0.size()));
+        HOPE_TRY(H, tv.reserve(n));
         double est = 0.0;
         for (int it = 0; it < 60 && !H.err; ++it) {
             apply_sym_op(H, 2, 1.0f, X2, 2, 1, tv, 1, X2 + 1, 2, 1.0f, nullptr, 0, 0.f, nullptr, 0);        // z = N^T N x
@@ -2575,7 +2552,6 @@ extern "C" int gemhip_lle(int64_t n, int64_t nnz, const int64_t *row_ptr, const 
             if (it >= 8 && std::fabs(est - prev) <= 1e-4 * est) break;                                     // the 5 % margin covers the rest
         }
         HOPE_TRY(H, hipStreamSynchronize(H.s));
-        hipFree(X2); hipFree(tv);
         if (H.err) return H.err;
         if (est > 0.0) c = est * 1.05;
         H.spmm_count = 0; H.spmm_cols = 0;
@@ -2657,16 +2633,13 @@ extern "C" int gemhip_hope_spmm(int64_t n, int64_t nnz, const int64_t *row_ptr, 
     Hope H; H.n = n; H.nnz = nnz;
     std::vector<float> va(std::max<int64_t>(nnz, 1), 1.0f);
     if (w) std::copy(w, w + nnz, va.begin());
-    float *dX = nullptr, *dW = nullptr, *dY = nullptr;
-    HOPE_TRY(H, hipMalloc((void **)&H.rp, (n + 1) * 8)); HOPE_TRY(H, hipMalloc((void **)&H.ci, std::max<int64_t>(nnz, 1) * 4)); HOPE_TRY(H, hipMalloc((void **)&H.va, std::max<int64_t>(nnz, 1) * 4));
-    HOPE_TRY(H, hipMalloc((void **)&dX, (size_t)n * b * 4)); HOPE_TRY(H, hipMalloc((void **)&dW, (size_t)n * b * 4)); HOPE_TRY(H, hipMalloc((void **)&dY, (size_t)n * b * 4));
-    HOPE_TRY(H, hipMemcpy(H.rp, row_ptr, (n + 1) * 8, hipMemcpyHostToDevice));
-    if (nnz) { HOPE_TRY(H, hipMemcpy(H.ci, col, nnz * 4, hipMemcpyHostToDevice)); HOPE_TRY(H, hipMemcpy(H.va, va.data(), nnz * 4, hipMemcpyHostToDevice)); }
-    HOPE_TRY(H, hipMemcpy(dX, X_host, (size_t)n * b * 4, hipMemcpyHostToDevice));
-    if (Wadd_host) HOPE_TRY(H, hipMemcpy(dW, Wadd_host, (size_t)n * b * 4, hipMemcpyHostToDevice));
-    spmm(H, false, alpha, dX, b, Wadd_host ? dW : nullptr, b, dY, b, b);
+    DevBuf<float> dX, dW, dY;
+    HOPE_TRY(H, H.rp.upload(row_ptr, n + 1)); HOPE_TRY(H, H.ci.upload(col, nnz)); HOPE_TRY(H, H.va.upload(va.data(), nnz));
+    HOPE_TRY(H, dX.upload(X_host, (size_t)n * b));
+    if (Wadd_host) HOPE_TRY(H, dW.upload(Wadd_host, (size_t)n * b));
+    HOPE_TRY(H, dY.reserve((size_t)n * b));
+    spmm(H, false, alpha, dX, b, dW, b, dY, b, b);
     HOPE_TRY(H, hipMemcpy(Y_host, dY, (size_t)n * b * 4, hipMemcpyDeviceToHost));
-    hipFree(dX); hipFree(dW); hipFree(dY);
     return H.err;
 }
 
@@ -2674,13 +2647,11 @@ extern "C" int gemhip_hope_gram(int64_t n, int32_t m1, int32_t m2, const float *
 {
     GEMHIP_REQUIRE(n >= 1 && m1 >= 1 && m2 >= 1 && X_host && Y_host && G_host, "hope_gram: bad arguments");
     Hope H; H.n = n;
-    float *dX = nullptr, *dY = nullptr;
-    HOPE_TRY(H, hipMalloc((void **)&dX, (size_t)n * m1 * 4)); HOPE_TRY(H, hipMalloc((void **)&dY, (size_t)n * m2 * 4));
-    HOPE_TRY(H, hipMemcpy(dX, X_host, (size_t)n * m1 * 4, hipMemcpyHostToDevice)); HOPE_TRY(H, hipMemcpy(dY, Y_host, (size_t)n * m2 * 4, hipMemcpyHostToDevice));
+    DevBuf<float> dX, dY;
+    HOPE_TRY(H, dX.upload(X_host, (size_t)n * m1)); HOPE_TRY(H, dY.upload(Y_host, (size_t)n * m2));
     std::vector<double> G;
     gram(H, dX, m1, m1, dY, m2, m2, G);
     if (!H.err) std::copy(G.begin(), G.end(), G_host);
-    hipFree(dX); hipFree(dY);
     return H.err;
 }
 
@@ -2689,13 +2660,12 @@ extern "C" int gemhip_hope_tsgemm(int64_t n, int32_t m, int32_t b2, const float 
 {
     GEMHIP_REQUIRE(n >= 1 && m >= 1 && b2 >= 1 && X_host && C_host && Out_host, "hope_tsgemm: bad arguments");
     Hope H; H.n = n;
-    float *dX = nullptr, *dS = nullptr, *dO = nullptr;
-    HOPE_TRY(H, hipMalloc((void **)&dX, (size_t)n * m * 4)); HOPE_TRY(H, hipMalloc((void **)&dS, (size_t)n * b2 * 4)); HOPE_TRY(H, hipMalloc((void **)&dO, (size_t)n * b2 * 4));
-    HOPE_TRY(H, hipMemcpy(dX, X_host, (size_t)n * m * 4, hipMemcpyHostToDevice));
-    if (Src_host) HOPE_TRY(H, hipMemcpy(dS, Src_host, (size_t)n * b2 * 4, hipMemcpyHostToDevice));
+    DevBuf<float> dX, dS, dO;
+    HOPE_TRY(H, dX.upload(X_host, (size_t)n * m));
+    if (Src_host) HOPE_TRY(H, dS.upload(Src_host, (size_t)n * b2));
+    HOPE_TRY(H, dO.reserve((size_t)n * b2));
     std::vector<double> C(C_host, C_host + (size_t)m * b2);
-    tsgemm(H, dX, m, m, C, b2, alpha, Src_host ? dS : nullptr, b2, dO, b2);
+    tsgemm(H, dX, m, m, C, b2, alpha, dS, b2, dO, b2);
     HOPE_TRY(H, hipMemcpy(Out_host, dO, (size_t)n * b2 * 4, hipMemcpyDeviceToHost));
-    hipFree(dX); hipFree(dS); hipFree(dO);
     return H.err;
 }

@@ -218,11 +218,8 @@ struct Fabric {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-struct DevBuf {          // frees on the device it was allocated on
-    void *p = nullptr; int dev = 0;
-    ~DevBuf() { if (p) { hipSetDevice(dev); hipFree(p); } }
-    int alloc(int device, size_t bytes) { dev = device; GEMHIP_CHECK(hipSetDevice(device)); GEMHIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); return GEMHIP_OK; }
-};
+using Bytes = DevBuf<char>;
+int alloc_on(Bytes &b, int device, size_t bytes) { GEMHIP_CHECK(hipSetDevice(device)); GEMHIP_CHECK(b.reserve(bytes)); return GEMHIP_OK; }
 
 }  // namespace
 
@@ -237,17 +234,17 @@ extern "C" int gemhip_rccl_selftest(int32_t n_gpus, const int32_t *devices, int6
     int rc = F.init(n_gpus, devices);
     const int N = n_gpus;
     const int64_t words = bytes / 4;
-    std::vector<DevBuf> G(N), A(N), S(N), Rv(N);
+    std::vector<Bytes> G(N), A(N), S(N), Rv(N);
     std::vector<void *> g(N), s(N), rv(N);
     std::vector<int32_t *> a(N);
     const double t0 = now_s();
     for (int r = 0; r < N && !rc; ++r) {
-        if (!rc) rc = G[r].alloc(F.dev[r], (size_t)bytes * N);
-        if (!rc) rc = A[r].alloc(F.dev[r], (size_t)bytes);
-        if (!rc) rc = S[r].alloc(F.dev[r], (size_t)bytes);
-        if (!rc) rc = Rv[r].alloc(F.dev[r], (size_t)bytes);
+        if (!rc) rc = alloc_on(G[r], F.dev[r], (size_t)bytes * N);
+        if (!rc) rc = alloc_on(A[r], F.dev[r], (size_t)bytes);
+        if (!rc) rc = alloc_on(S[r], F.dev[r], (size_t)bytes);
+        if (!rc) rc = alloc_on(Rv[r], F.dev[r], (size_t)bytes);
         if (rc) break;
-        g[r] = G[r].p; a[r] = (int32_t *)A[r].p; s[r] = S[r].p; rv[r] = Rv[r].p;
+        g[r] = G[r].get(); a[r] = (int32_t *)A[r].get(); s[r] = S[r].get(); rv[r] = Rv[r].get();
         std::vector<int32_t> h((size_t)words * N, -1), hb((size_t)words);
         for (int64_t i = 0; i < words; ++i) { h[(size_t)r * words + i] = (int32_t)(1000003 * r + i); hb[i] = (int32_t)((r + 1) * (i % 97 + 1)); }
         if (hipMemcpy(g[r], h.data(), (size_t)bytes * N, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(a[r], hb.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
@@ -305,7 +302,7 @@ extern "C" int gemhip_gf_train_multi(int64_t n, int64_t m, const int32_t *src, c
     const int N = n_gpus;
     const int64_t block = (n + N - 1) / N, n_pad = block * N;
     std::vector<gemhip_gf_plan_t> plan(N, nullptr);
-    std::vector<DevBuf> Xa(N), Xb(N);
+    std::vector<Bytes> Xa(N), Xb(N);
     std::vector<float> Xpad;
     if (!rc && n_pad != n) { Xpad.assign((size_t)n_pad * d, 0.f); std::memcpy(Xpad.data(), X_inout, (size_t)n * d * sizeof(float)); }
     const float *Xsrc = n_pad != n ? Xpad.data() : X_inout;
@@ -314,12 +311,12 @@ extern "C" int gemhip_gf_train_multi(int64_t n, int64_t m, const int32_t *src, c
         rc = F.use(r);
         const int64_t r0 = std::min<int64_t>(r * block, n), r1 = std::min<int64_t>((r + 1) * block, n);
         if (!rc) rc = gemhip_gf_plan_create(n, m, src, dst, w, d, r0, r1, &plan[r]);
-        if (!rc) rc = Xa[r].alloc(F.dev[r], (size_t)n_pad * d * sizeof(float));
-        if (!rc) rc = Xb[r].alloc(F.dev[r], (size_t)n_pad * d * sizeof(float));
-        if (!rc && (hipMemcpy(Xa[r].p, Xsrc, (size_t)n_pad * d * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(Xb[r].p, Xa[r].p, (size_t)n_pad * d * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess))
+        if (!rc) rc = alloc_on(Xa[r], F.dev[r], (size_t)n_pad * d * sizeof(float));
+        if (!rc) rc = alloc_on(Xb[r], F.dev[r], (size_t)n_pad * d * sizeof(float));
+        if (!rc && (hipMemcpy(Xa[r].get(), Xsrc, (size_t)n_pad * d * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(Xb[r].get(), Xa[r].get(), (size_t)n_pad * d * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess))
             rc = fail(GEMHIP_E_HIP, "gf_train_multi: table upload failed on rank %d", r);
-        if (!rc) rc = gemhip_gf_plan_bind(plan[r], Xa[r].p, Xb[r].p);
+        if (!rc) rc = gemhip_gf_plan_bind(plan[r], Xa[r].get(), Xb[r].get());
         int64_t info[8];
         if (!rc) { rc = gemhip_gf_plan_info(plan[r], info); upd += (double)info[0]; rows += (double)info[1]; }
     }
@@ -387,14 +384,14 @@ extern "C" int gemhip_n2v_train_multi(int64_t n, int64_t nnz, const int64_t *row
     int64_t shard_rows = 1;
     for (int r = 0; r < N; ++r) { int64_t lo, hi; shard(r, lo, hi); shard_rows = std::max(shard_rows, hi - lo); }
     const size_t shard_bytes = (size_t)shard_rows * walk_len * sizeof(int32_t);
-    std::vector<DevBuf> corpus(N), segd(N), Pp(N), Na(N), Nb(N);
+    std::vector<Bytes> corpus(N), segd(N), Pp(N), Na(N), Nb(N);
     std::vector<void *> cptr(N);
     for (int r = 0; r < N && !rc; ++r) {
         int64_t lo, hi; shard(r, lo, hi);
-        rc = corpus[r].alloc(F.dev[r], shard_bytes * N);
-        if (!rc && hipMemsetAsync((char *)corpus[r].p + (size_t)r * shard_bytes, 0xff, shard_bytes, F.st[r]) != hipSuccess) rc = fail(GEMHIP_E_HIP, "n2v_train_multi: memset");
-        if (!rc) rc = gemhip_n2v_copy_walks(h[r], 0, hi - lo, (char *)corpus[r].p + (size_t)r * shard_bytes, F.st[r]);
-        cptr[r] = corpus[r].p;
+        rc = alloc_on(corpus[r], F.dev[r], shard_bytes * N);
+        if (!rc && hipMemsetAsync((char *)corpus[r].get() + (size_t)r * shard_bytes, 0xff, shard_bytes, F.st[r]) != hipSuccess) rc = fail(GEMHIP_E_HIP, "n2v_train_multi: memset");
+        if (!rc) rc = gemhip_n2v_copy_walks(h[r], 0, hi - lo, (char *)corpus[r].get() + (size_t)r * shard_bytes, F.st[r]);
+        cptr[r] = corpus[r].get();
     }
     if (!rc) rc = F.all_gather_inplace(cptr, shard_bytes);
     // ---- the per-partition unigram tables, in the layout the flags ask for: node-id order, or (GEMHIP_N2V_VOCAB_ORDER, the plugin default on one GPU)
@@ -402,13 +399,13 @@ extern "C" int gemhip_n2v_train_multi(int64_t n, int64_t nnz, const int64_t *row
     if (!rc) rc = F.sync_all();
     for (int r = 0; r < N && !rc; ++r) {
         rc = F.use(r);
-        if (!rc) rc = (flags & GEMHIP_N2V_VOCAB_ORDER) ? gemhip_n2v_build_unigram_parts_vocab_order(h[r], N, flags, corpus[r].p, (int64_t)N * shard_rows * walk_len, nullptr, nullptr, nullptr, nullptr)
+        if (!rc) rc = (flags & GEMHIP_N2V_VOCAB_ORDER) ? gemhip_n2v_build_unigram_parts_vocab_order(h[r], N, flags, corpus[r].get(), (int64_t)N * shard_rows * walk_len, nullptr, nullptr, nullptr, nullptr)
                                                        : gemhip_n2v_build_unigram_parts(h[r], N, nullptr, nullptr);
     }
     // ---- LOCALLY HOT ROWS of the gathered corpus (nodes whose tokens are packed into few walks: the ends of isolated edges): never cached by the bucket launches
     for (int r = 0; r < N && !rc; ++r) {
         rc = F.use(r);
-        if (!rc) rc = gemhip_n2v_locally_hot_corpus(h[r], corpus[r].p, (int64_t)N * shard_rows, walk_len, -1, nullptr, F.st[r]);
+        if (!rc) rc = gemhip_n2v_locally_hot_corpus(h[r], corpus[r].get(), (int64_t)N * shard_rows, walk_len, -1, nullptr, F.st[r]);
     }
     // ---- episode table [episodes][3][N]: first row, walks present, first global walk id of every shard's slice; work items per shard = longest slice
     std::vector<int64_t> tab((size_t)episodes * 3 * N), seg_len(episodes, 1);
@@ -425,12 +422,12 @@ extern "C" int gemhip_n2v_train_multi(int64_t n, int64_t nnz, const int64_t *row
     const size_t part_bytes = (size_t)prow * d * sizeof(float);
     for (int r = 0; r < N && !rc; ++r) {
         rc = F.use(r);
-        if (!rc) rc = segd[r].alloc(F.dev[r], tab.size() * sizeof(int64_t));
-        if (!rc && hipMemcpy(segd[r].p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) rc = fail(GEMHIP_E_HIP, "n2v_train_multi: table upload");
+        if (!rc) rc = alloc_on(segd[r], F.dev[r], tab.size() * sizeof(int64_t));
+        if (!rc && hipMemcpy(segd[r].get(), tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) rc = fail(GEMHIP_E_HIP, "n2v_train_multi: table upload");
         if (!rc && r == 0) rc = gemhip_sgns_init(h[0], d, seed, nullptr, nullptr);       // InitPosEmb / InitNegEmb of the whole table, once (rank 0's device)
-        if (!rc) rc = Pp[r].alloc(F.dev[r], part_bytes);
-        if (!rc) rc = Na[r].alloc(F.dev[r], part_bytes);
-        if (!rc) rc = Nb[r].alloc(F.dev[r], part_bytes);
+        if (!rc) rc = alloc_on(Pp[r], F.dev[r], part_bytes);
+        if (!rc) rc = alloc_on(Na[r], F.dev[r], part_bytes);
+        if (!rc) rc = alloc_on(Nb[r], F.dev[r], part_bytes);
     }
     // the partitions are cut out of a host copy of that table (the handle keeps its tables private; get_tables synchronises the device)
     if (!rc) {
@@ -441,8 +438,8 @@ extern "C" int gemhip_n2v_train_multi(int64_t n, int64_t nnz, const int64_t *row
             std::fill(part.begin(), part.end(), 0.f);
             for (int64_t l = 0; l * N + r < n; ++l) std::memcpy(&part[(size_t)l * d], &full[(size_t)(l * N + r) * d], (size_t)d * sizeof(float));
             hipSetDevice(F.dev[r]);
-            if (hipMemcpy(Pp[r].p, part.data(), part_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemset(Na[r].p, 0, part_bytes) != hipSuccess ||
-                hipMemset(Nb[r].p, 0, part_bytes) != hipSuccess)
+            if (hipMemcpy(Pp[r].get(), part.data(), part_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemset(Na[r].get(), 0, part_bytes) != hipSuccess ||
+                hipMemset(Nb[r].get(), 0, part_bytes) != hipSuccess)
                 rc = fail(GEMHIP_E_HIP, "n2v_train_multi: partition upload failed on rank %d", r);
         }
     }
@@ -450,7 +447,7 @@ extern "C" int gemhip_n2v_train_multi(int64_t n, int64_t nnz, const int64_t *row
     const double t1 = now_s();
     // ---- episodes x rounds: bucket (r, (r + s) % N) on rank r, then the SynNeg partitions move one step around the ring
     std::vector<void *> ncur(N), ntmp(N);
-    for (int r = 0; r < N; ++r) { ncur[r] = Na[r].p; ntmp[r] = Nb[r].p; }
+    for (int r = 0; r < N; ++r) { ncur[r] = Na[r].get(); ntmp[r] = Nb[r].get(); }
     int64_t alpha_total = 0;
     for (int e = 0; e < episodes; ++e) alpha_total += seg_len[e] * N * walk_len;
     alpha_total *= epochs;
@@ -460,8 +457,8 @@ extern "C" int gemhip_n2v_train_multi(int64_t n, int64_t nnz, const int64_t *row
             for (int s = 0; s < N && !rc; ++s) {
                 for (int r = 0; r < N && !rc; ++r) {
                     rc = F.use(r);
-                    if (!rc) rc = gemhip_sgns_train_part(h[r], corpus[r].p, (int64_t)N * seg_len[e], walk_len, (const int64_t *)segd[r].p + (size_t)e * 3 * N, N, seg_len[e], 0, window,
-                                                         0.025f, alpha_total, done, ep, seed, flags, r, (r + s) % N, Pp[r].p, ncur[r], d, F.st[r]);
+                    if (!rc) rc = gemhip_sgns_train_part(h[r], corpus[r].get(), (int64_t)N * seg_len[e], walk_len, (const int64_t *)segd[r].get() + (size_t)e * 3 * N, N, seg_len[e], 0, window,
+                                                         0.025f, alpha_total, done, ep, seed, flags, r, (r + s) % N, Pp[r].get(), ncur[r], d, F.st[r]);
                     ++launches;
                 }
                 if (!rc && N > 1) { rc = F.ring_shift(ncur, ntmp, part_bytes); std::swap(ncur, ntmp); }
@@ -476,7 +473,7 @@ extern "C" int gemhip_n2v_train_multi(int64_t n, int64_t nnz, const int64_t *row
         std::vector<float> part((size_t)prow * d);
         for (int r = 0; r < N && !rc; ++r) {
             hipSetDevice(F.dev[r]);
-            if (hipMemcpy(part.data(), Pp[r].p, part_bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GEMHIP_E_HIP, "n2v_train_multi: download failed on rank %d", r); break; }
+            if (hipMemcpy(part.data(), Pp[r].get(), part_bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GEMHIP_E_HIP, "n2v_train_multi: download failed on rank %d", r); break; }
             for (int64_t l = 0; l * N + r < n; ++l) std::memcpy(X_out + (size_t)(l * N + r) * d, &part[(size_t)l * d], (size_t)d * sizeof(float));
             int64_t pr = 0;
             rc = gemhip_sgns_pairs(h[r], &pr, 1);

@@ -135,58 +135,57 @@ struct gemhip_n2v {
     int64_t n = 0, nnz = 0;
     int device = 0;
     bool uniform_rows = true;         // every row has equal weights -> no alias tables needed
-    int64_t *d_row_ptr = nullptr;
-    int32_t *d_col = nullptr;         // columns sorted inside each row
+    DevBuf<int64_t> d_row_ptr;
+    DevBuf<int32_t> d_col;            // columns sorted inside each row
     // walk start nodes: the nodes that occur in the edge list (the reference binary only knows those; an isolated node
     // never reaches it).  start[0..m_start) ascending; walk id r*m_start + j starts at start[perm_r(j)]
     int64_t m_start = 0;
-    int32_t *d_start = nullptr;
-    float *d_w = nullptr;
+    DevBuf<int32_t> d_start;
+    DevBuf<float> d_w;
     std::vector<int32_t> hub_rows;    // rows with at least ALIAS_HUB_DEG neighbours (n2v_alias_hub_kernel builds their tables: a workgroup per row)
     std::vector<int64_t> hub_off;     // ... and the offset of each one's scratch segment (prefix sum of their degrees)
-    float *d_U = nullptr;             // first-order alias tables (per-row segments)
-    int32_t *d_K = nullptr;
+    DevBuf<float> d_U;                // first-order alias tables (per-row segments)
+    DevBuf<int32_t> d_K;
     // walks
-    int32_t *d_walks = nullptr;
-    int64_t walks_cap = 0;            // tokens allocated
+    DevBuf<int32_t> d_walks;          // capacity in tokens
     int64_t nwalks = 0;               // local walks held
     int32_t walk_len = 0;
     int64_t walk_id_offset = 0;       // global id of local walk 0
     // vocabulary / unigram
-    int32_t *d_counts = nullptr;
-    float *d_UT = nullptr;
-    int32_t *d_KT = nullptr;
-    uint2 *d_UK = nullptr;             // {bits of UT[i], KT[i]} interleaved: one 8-byte gather instead of two 4-byte gathers
+    int32_t *d_counts = nullptr;      // what the kernels read: counts_own's block, or the caller's (gemhip_n2v_bind_counts)
+    DevBuf<int32_t> counts_own;       // empty while the counts are borrowed
+    DevBuf<float> d_UT;
+    DevBuf<int32_t> d_KT;
+    DevBuf<uint2> d_UK;                // {bits of UT[i], KT[i]} interleaved: one 8-byte gather instead of two 4-byte gathers
     bool unigram_ready = false;
     // slot tables of the window kernels (SgnsArgs::SK): {X, UT[X], KT[X]} by SLOT, built on the device from the tables above on the first launch
     // after a table build, once per RndUnigramInt-quirk setting (sk_state / skp_state: -1 stale, else the quirk bit they were built for)
-    uint4 *d_SK = nullptr; int64_t sk_cap = 0; int sk_state = -1;
-    uint4 *d_SKp = nullptr; int skp_state = -1;
+    DevBuf<uint4> d_SK; int sk_state = -1;
+    DevBuf<uint4> d_SKp; int skp_state = -1;
     // vocabulary-order layout (gemhip_n2v_build_unigram_vocab_order): the slot table of RndUnigramInt, and how many slots it has
-    int32_t *d_KTslot = nullptr; int64_t n_vocab = 0; bool vocab_order = false;
-    unsigned long long *d_first = nullptr;   // first token index of every node (scratch of that builder)
+    DevBuf<int32_t> d_KTslot; int64_t n_vocab = 0; bool vocab_order = false;
+    DevBuf<unsigned long long> d_first;      // first token index of every node (scratch of that builder)
     // embeddings
     int32_t d = 0;
-    float *SynPos = nullptr, *SynNeg = nullptr;
-    bool own_syn = false;
+    float *SynPos = nullptr, *SynNeg = nullptr;   // what the kernels train: syn_own's blocks, or the caller's tables (gemhip_sgns_init)
+    DevBuf<float> syn_own[2];         // empty while the tables are borrowed
     SgnsKnobs kn;                     // launch knobs (setters below; environment overrides read once in gemhip_n2v_create)
-    int32_t *d_hotkey = nullptr; int32_t *d_wcount = nullptr; unsigned int *d_nlocal = nullptr; int hotkey_state = 0; int64_t n_local_hot = 0;   // LOCALLY HOT ROWS (ensure_hotkey)
+    DevBuf<int32_t> d_hotkey, d_wcount; DevBuf<unsigned int> d_nlocal; int hotkey_state = 0; int64_t n_local_hot = 0;   // LOCALLY HOT ROWS (ensure_hotkey)
     SgnsLaunchPlan last_plan;         // what the last gemhip_sgns_train / _train_part on this handle actually launched (gemhip_sgns_last_launch)
     int32_t last_fresh = 0;
     VocabStats vs;                    // vocabulary statistics (gemhip_n2v_build_unigram*): how concentrated the row traffic is -> plan_sgns_launch
-    float *d_dummy = nullptr; size_t dummy_bytes = 0;   // sgns_win_kernel: one scratch row per wavefront
-    float *d_scratch = nullptr; size_t scratch_bytes = 0;   // sgns_win_kernel<PART>: the window rows as loaded, 2R+1 rows per wavefront
-    unsigned long long *d_pairs = nullptr;   // (centre,context) pairs trained so far
+    DevBuf<float> d_dummy;       // sgns_win_kernel: one scratch row per wavefront
+    DevBuf<float> d_scratch;     // sgns_win_kernel<PART>: the window rows as loaded, 2R+1 rows per wavefront
+    DevBuf<unsigned long long> d_pairs;      // (centre,context) pairs trained so far
     // per-partition unigram tables (multi-GPU episode schedule): partition p = {v : v % parts == p}, local index v / parts
     int32_t parts = 0;
-    float *d_UTp = nullptr; int32_t *d_KTp = nullptr;
-    uint2 *d_UKp = nullptr;                  // {bits of UTp[i], KTp[i]} interleaved (sgns_win_kernel<PART>)
+    DevBuf<float> d_UTp; DevBuf<int32_t> d_KTp;
+    DevBuf<uint2> d_UKp;                     // {bits of UTp[i], KTp[i]} interleaved (sgns_win_kernel<PART>)
     // ... in the binary's layout (gemhip_n2v_build_unigram_parts_vocab_order): per partition the slot table of RndUnigramInt in LOCAL indices
     // (d_KTslotp[part_off[p] + slot]) and its number of slots (the partition's nodes that occur); the alias arrays above are then indexed by local row
-    int32_t *d_KTslotp = nullptr; std::vector<int64_t> part_slots; bool parts_vocab_order = false;
+    DevBuf<int32_t> d_KTslotp; std::vector<int64_t> part_slots; bool parts_vocab_order = false;
     std::vector<int64_t> part_off;           // table p occupies [part_off[p], part_off[p+1])
     std::vector<VocabStats> vs_part;         // vocabulary statistics of each partition's rows (launch rule of gemhip_sgns_train_part)
-    bool own_counts = true;
 };
 
 namespace {
@@ -549,18 +548,13 @@ extern "C" int gemhip_n2v_create(int64_t n, int64_t nnz, const int64_t *row_ptr,
     if (hipGetDevice(&h->device) != hipSuccess) { delete h; return fail(GEMHIP_E_HIP, "n2v_create: no HIP device"); }
     phase_acc()[PH_HOST] += phase_now() - t_host0;
     PhaseScope ph_up(PH_H2D);
-    hipError_t e = hipMalloc((void **)&h->d_row_ptr, (n + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMemcpy(h->d_row_ptr, row_ptr, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_col, std::max<int64_t>(nnz, 4) * sizeof(int32_t));
-    if (e == hipSuccess && nnz) e = hipMemcpy(h->d_col, c.data(), nnz * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !uniform) {
-        e = hipMalloc((void **)&h->d_w, nnz * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(h->d_w, ww.data(), nnz * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_start, std::max<size_t>(start.size(), 4) * sizeof(int32_t));
-    if (e == hipSuccess && !start.empty()) e = hipMemcpy(h->d_start, start.data(), start.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_counts, n * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_pairs, sizeof(unsigned long long));
+    hipError_t e = h->d_row_ptr.upload(row_ptr, n + 1);
+    if (e == hipSuccess) e = h->d_col.upload(c.data(), nnz);
+    if (e == hipSuccess && !uniform) e = h->d_w.upload(ww.data(), nnz);
+    if (e == hipSuccess) e = h->d_start.upload(start.data(), start.size());
+    if (e == hipSuccess) e = h->counts_own.reserve(n);
+    h->d_counts = h->counts_own;
+    if (e == hipSuccess) e = h->d_pairs.reserve(1);
     if (e == hipSuccess) e = hipMemset(h->d_pairs, 0, sizeof(unsigned long long));
     if (e != hipSuccess) { gemhip_n2v_destroy(h); return fail(GEMHIP_E_HIP, "n2v_create: device upload failed: %s", hipGetErrorString(e)); }
     *out = h;
@@ -570,12 +564,6 @@ extern "C" int gemhip_n2v_create(int64_t n, int64_t nnz, const int64_t *row_ptr,
 extern "C" int gemhip_n2v_destroy(gemhip_n2v_t h)
 {
     if (!h) return GEMHIP_OK;
-    hipFree(h->d_start);
-    hipFree(h->d_row_ptr); hipFree(h->d_col); hipFree(h->d_w); hipFree(h->d_U); hipFree(h->d_K); hipFree(h->d_walks); hipFree(h->d_dummy); hipFree(h->d_scratch);
-    if (h->own_counts) hipFree(h->d_counts);
-    hipFree(h->d_hotkey); hipFree(h->d_wcount); hipFree(h->d_nlocal);
-    hipFree(h->d_UT); hipFree(h->d_KT); hipFree(h->d_UK); hipFree(h->d_SK); hipFree(h->d_SKp); hipFree(h->d_KTslot); hipFree(h->d_first); hipFree(h->d_pairs); hipFree(h->d_UTp); hipFree(h->d_KTp); hipFree(h->d_UKp); hipFree(h->d_KTslotp);
-    if (h->own_syn) { hipFree(h->SynPos); hipFree(h->SynNeg); }
     delete h;
     return GEMHIP_OK;
 }
@@ -584,29 +572,28 @@ extern "C" int gemhip_n2v_build_alias(gemhip_n2v_t h, void *stream)
 {
     GEMHIP_REQUIRE(h, "n2v_build_alias: NULL handle");
     if (h->uniform_rows || h->d_U) return GEMHIP_OK;
-    int32_t *work = nullptr;
-    GEMHIP_CHECK(hipMalloc((void **)&h->d_U, h->nnz * sizeof(float)));
-    GEMHIP_CHECK(hipMalloc((void **)&h->d_K, h->nnz * sizeof(int32_t)));
-    GEMHIP_CHECK(hipMalloc((void **)&work, h->nnz * sizeof(int32_t)));
+    // built in locals and handed to the handle only when complete: an error exit leaves the handle without tables (the next call builds again)
+    DevBuf<float> U; DevBuf<int32_t> K, work, d_hubs; DevBuf<int64_t> d_hoff; DevBuf<unsigned char> d_scr;
+    GEMHIP_CHECK(U.reserve(h->nnz));
+    GEMHIP_CHECK(K.reserve(h->nnz));
+    GEMHIP_CHECK(work.reserve(h->nnz));
     hipLaunchKernelGGL(n2v_alias_rows_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->n,
-                       h->d_row_ptr, h->d_w, h->d_U, h->d_K, work);
+                       h->d_row_ptr, h->d_w, U, K, work);
     GEMHIP_CHECK(hipGetLastError());
-    int32_t *d_hubs = nullptr; int64_t *d_hoff = nullptr; unsigned char *d_scr = nullptr;
     if (!h->hub_rows.empty()) {                        // hub rows: a workgroup each (the one-lane kernel skipped them)
         const size_t nh = h->hub_rows.size();
         const size_t entries = (size_t)h->hub_off.back();
         const size_t scr_bytes = entries * 24 + (entries / ALIAS_CHUNK + nh + 1) * 24;
-        GEMHIP_CHECK(hipMalloc((void **)&d_hubs, nh * sizeof(int32_t)));
-        GEMHIP_CHECK(hipMalloc((void **)&d_hoff, (nh + 1) * sizeof(int64_t)));
-        GEMHIP_CHECK(hipMalloc((void **)&d_scr, scr_bytes));
+        GEMHIP_CHECK(d_hubs.reserve(nh));
+        GEMHIP_CHECK(d_hoff.reserve(nh + 1));
+        GEMHIP_CHECK(d_scr.reserve(scr_bytes));
         GEMHIP_CHECK(hipMemcpyAsync(d_hubs, h->hub_rows.data(), nh * sizeof(int32_t), hipMemcpyHostToDevice, (hipStream_t)stream));
         GEMHIP_CHECK(hipMemcpyAsync(d_hoff, h->hub_off.data(), (nh + 1) * sizeof(int64_t), hipMemcpyHostToDevice, (hipStream_t)stream));
-        hipLaunchKernelGGL(n2v_alias_hub_kernel, dim3((unsigned)nh), dim3(256), 0, (hipStream_t)stream, d_hubs, d_hoff, h->d_row_ptr, h->d_w, h->d_U, h->d_K, d_scr);
+        hipLaunchKernelGGL(n2v_alias_hub_kernel, dim3((unsigned)nh), dim3(256), 0, (hipStream_t)stream, d_hubs, d_hoff, h->d_row_ptr, h->d_w, U, K, d_scr);
         GEMHIP_CHECK(hipGetLastError());
     }
     GEMHIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    GEMHIP_CHECK(hipFree(work));
-    hipFree(d_hubs); hipFree(d_hoff); hipFree(d_scr);
+    h->d_U = std::move(U); h->d_K = std::move(K);
     return GEMHIP_OK;
 }
 
@@ -624,11 +611,7 @@ extern "C" int gemhip_n2v_get_alias(gemhip_n2v_t h, float *U_host, int32_t *K_ho
 static int ensure_walk_buffer(gemhip_n2v_t h, int64_t nwalks, int32_t walk_len)
 {
     const int64_t need = nwalks * walk_len;
-    if (need > h->walks_cap) {
-        hipFree(h->d_walks); h->d_walks = nullptr; h->walks_cap = 0;
-        GEMHIP_CHECK(hipMalloc((void **)&h->d_walks, std::max<int64_t>(need, 4) * sizeof(int32_t)));
-        h->walks_cap = need;
-    }
+    if ((size_t)need > h->d_walks.capacity()) GEMHIP_CHECK(h->d_walks.reserve(need));          // (no walks asked for and none held: stays empty)
     h->nwalks = nwalks; h->walk_len = walk_len;
     return GEMHIP_OK;
 }
@@ -715,8 +698,8 @@ extern "C" int gemhip_n2v_vocab(gemhip_n2v_t h, void *stream)
 extern "C" int gemhip_n2v_bind_counts(gemhip_n2v_t h, void *d_counts)
 {
     GEMHIP_REQUIRE(h && d_counts, "n2v_bind_counts: NULL argument");
-    if (h->own_counts) hipFree(h->d_counts);
-    h->d_counts = (int32_t *)d_counts; h->own_counts = false; h->unigram_ready = false; h->hotkey_state = 0;
+    h->counts_own.reset();
+    h->d_counts = (int32_t *)d_counts; h->unigram_ready = false; h->hotkey_state = 0;
     return GEMHIP_OK;
 }
 
@@ -782,15 +765,12 @@ extern "C" int gemhip_n2v_build_unigram(gemhip_n2v_t h, int32_t *counts_out, flo
         h->vs.build(cnt.data(), (int64_t)cnt.size());
     }
     PhaseScope ph_up(PH_H2D);
-    if (!h->d_UT) GEMHIP_CHECK(hipMalloc((void **)&h->d_UT, n * sizeof(float)));
-    if (!h->d_KT) GEMHIP_CHECK(hipMalloc((void **)&h->d_KT, n * sizeof(int32_t)));
-    GEMHIP_CHECK(hipMemcpy(h->d_UT, Uf.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    GEMHIP_CHECK(hipMemcpy(h->d_KT, K.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+    GEMHIP_CHECK(h->d_UT.upload(Uf.data(), n));
+    GEMHIP_CHECK(h->d_KT.upload(K.data(), n));
     {
         std::vector<uint2> UK((size_t)n);
         for (int64_t i = 0; i < n; ++i) { uint32_t ub; memcpy(&ub, &Uf[i], 4); UK[i] = make_uint2(ub, (uint32_t)K[i]); }
-        if (!h->d_UK) GEMHIP_CHECK(hipMalloc((void **)&h->d_UK, n * sizeof(uint2)));
-        GEMHIP_CHECK(hipMemcpy(h->d_UK, UK.data(), n * sizeof(uint2), hipMemcpyHostToDevice));
+        GEMHIP_CHECK(h->d_UK.upload(UK.data(), n));
     }
     h->unigram_ready = true; h->vocab_order = false; h->sk_state = -1; h->hotkey_state = 0;
     if (counts_out) std::copy(cnt.begin(), cnt.end(), counts_out);
@@ -807,24 +787,23 @@ static int first_appearance_order(gemhip_n2v_t h, const int32_t *d_tokens, int64
     // below go to the null stream, which does not wait for such a stream
     GEMHIP_CHECK(hipDeviceSynchronize());
     const int64_t n = h->n;
-    if (!h->d_first) GEMHIP_CHECK(hipMalloc((void **)&h->d_first, n * sizeof(unsigned long long)));
+    GEMHIP_CHECK(h->d_first.reserve(n));
     GEMHIP_CHECK(hipMemset(h->d_first, 0xff, n * sizeof(unsigned long long)));
     hipLaunchKernelGGL(n2v_first_token_kernel, dim3((unsigned)std::min<int64_t>((ntok + 255) / 256, 256 * 16)), dim3(256), 0, 0, d_tokens, ntok, h->d_first);
     GEMHIP_CHECK(hipGetLastError());
     // nodes sorted by their first token index on the device (radix sort of (first, node) pairs: nodes that never occur sort last)
     back.assign(n, 0); cnt.assign(n, 0);
-    unsigned long long *keys_out = nullptr; int32_t *ids = nullptr, *ids_out = nullptr; void *tmp = nullptr; size_t tmp_bytes = 0;
-    hipError_t e = hipMalloc((void **)&keys_out, n * sizeof(unsigned long long));          // (every exit below frees all three temporaries)
-    if (e == hipSuccess) e = hipMalloc((void **)&ids, 2 * n * sizeof(int32_t));
-    ids_out = ids + n;
+    DevBuf<unsigned long long> keys_out; DevBuf<int32_t> ids; DevBuf<char> tmp; size_t tmp_bytes = 0;
+    hipError_t e = keys_out.reserve(n);
+    if (e == hipSuccess) e = ids.reserve(2 * n);
+    int32_t *ids_out = ids + n;
     if (e == hipSuccess) { hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ids, n); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, h->d_first, keys_out, ids, ids_out, (int)n);
-    if (e == hipSuccess) e = hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 16));
-    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, h->d_first, keys_out, ids, ids_out, (int)n);
+    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, h->d_first.get(), keys_out.get(), ids.get(), ids_out, (int)n);
+    if (e == hipSuccess) e = tmp.reserve(tmp_bytes);
+    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(tmp.get(), tmp_bytes, h->d_first.get(), keys_out.get(), ids.get(), ids_out, (int)n);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) { PhaseScope ph(PH_D2H); e = hipMemcpy(back.data(), ids_out, n * sizeof(int32_t), hipMemcpyDeviceToHost);
                            if (e == hipSuccess) e = hipMemcpy(cnt.data(), h->d_counts, n * sizeof(int32_t), hipMemcpyDeviceToHost); }
-    hipFree(keys_out); hipFree(ids); hipFree(tmp);
     if (e != hipSuccess) return fail(GEMHIP_E_HIP, "first_appearance_order: device sort failed: %s", hipGetErrorString(e));
     return GEMHIP_OK;
 }
@@ -862,11 +841,10 @@ extern "C" int gemhip_n2v_build_unigram_vocab_order(gemhip_n2v_t h, int32_t flag
         uint32_t ub; memcpy(&ub, &Uf[r], 4);
         UK[back[r]] = make_uint2(ub, (uint32_t)back[K[r]]);
     }
-    if (!h->d_KTslot) GEMHIP_CHECK(hipMalloc((void **)&h->d_KTslot, n * sizeof(int32_t)));
-    if (!h->d_UK) GEMHIP_CHECK(hipMalloc((void **)&h->d_UK, n * sizeof(uint2)));
+    GEMHIP_CHECK(h->d_KTslot.reserve(n));
     { PhaseScope ph(PH_H2D);
       GEMHIP_CHECK(hipMemcpy(h->d_KTslot, slot.data(), N * sizeof(int32_t), hipMemcpyHostToDevice));
-      GEMHIP_CHECK(hipMemcpy(h->d_UK, UK.data(), n * sizeof(uint2), hipMemcpyHostToDevice)); }
+      GEMHIP_CHECK(h->d_UK.upload(UK.data(), n)); }
     h->n_vocab = N; h->vocab_order = true; h->unigram_ready = true; h->sk_state = -1; h->hotkey_state = 0;
     if (n_vocab_out) *n_vocab_out = N;
     if (order_out) std::copy(back.begin(), back.end(), order_out);
@@ -900,19 +878,14 @@ extern "C" int gemhip_n2v_build_unigram_parts(gemhip_n2v_t h, int32_t parts, flo
         for (int64_t i = 0; i < np; ++i) cp[i] = cnt[p + i * parts];
         h->vs_part[p].build(cp.data(), np);
     }
-    hipFree(h->d_UTp); hipFree(h->d_KTp); hipFree(h->d_UKp); h->d_UTp = nullptr; h->d_KTp = nullptr; h->d_UKp = nullptr;
-    GEMHIP_CHECK(hipMalloc((void **)&h->d_UTp, n * sizeof(float)));
-    GEMHIP_CHECK(hipMalloc((void **)&h->d_KTp, n * sizeof(int32_t)));
-    GEMHIP_CHECK(hipMalloc((void **)&h->d_UKp, n * sizeof(uint2)));
-    GEMHIP_CHECK(hipMemcpy(h->d_UTp, Uall.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    GEMHIP_CHECK(hipMemcpy(h->d_KTp, Kall.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+    GEMHIP_CHECK(h->d_UTp.upload(Uall.data(), n));
+    GEMHIP_CHECK(h->d_KTp.upload(Kall.data(), n));
     {
         std::vector<uint2> UK((size_t)n);
         for (int64_t i = 0; i < n; ++i) { uint32_t ub; memcpy(&ub, &Uall[i], 4); UK[i] = make_uint2(ub, (uint32_t)Kall[i]); }
-        GEMHIP_CHECK(hipMemcpy(h->d_UKp, UK.data(), n * sizeof(uint2), hipMemcpyHostToDevice));
+        GEMHIP_CHECK(h->d_UKp.upload(UK.data(), n));
     }
     h->parts = parts; h->skp_state = -1; h->parts_vocab_order = false;
-    hipFree(h->d_SKp); h->d_SKp = nullptr;
     if (UT_out) std::copy(Uall.begin(), Uall.end(), UT_out);
     if (KT_out) std::copy(Kall.begin(), Kall.end(), KT_out);
     return GEMHIP_OK;
@@ -960,24 +933,18 @@ extern "C" int gemhip_n2v_build_unigram_parts_vocab_order(gemhip_n2v_t h, int32_
         for (int64_t i = 0; i < np; ++i) cp[i] = cnt[p + i * parts];
         h->vs_part[p].build(cp.data(), np);
     }
-    hipFree(h->d_UTp); hipFree(h->d_KTp); hipFree(h->d_UKp); hipFree(h->d_KTslotp); h->d_UTp = nullptr; h->d_KTp = nullptr; h->d_UKp = nullptr; h->d_KTslotp = nullptr;
-    GEMHIP_CHECK(hipMalloc((void **)&h->d_UTp, n * sizeof(float)));
-    GEMHIP_CHECK(hipMalloc((void **)&h->d_KTp, n * sizeof(int32_t)));
-    GEMHIP_CHECK(hipMalloc((void **)&h->d_UKp, n * sizeof(uint2)));
-    GEMHIP_CHECK(hipMalloc((void **)&h->d_KTslotp, n * sizeof(int32_t)));
     {
         PhaseScope ph(PH_H2D);
         std::vector<uint2> UK((size_t)n);
         for (int64_t i = 0; i < n; ++i) { uint32_t ub; memcpy(&ub, &Uall[i], 4); UK[i] = make_uint2(ub, (uint32_t)Kall[i]); }
         std::vector<int32_t> Sdev(Sall);
         for (auto &v : Sdev) if (v < 0) v = 0;                 // (never read: a partition's launches draw slots below its slot count)
-        GEMHIP_CHECK(hipMemcpy(h->d_UTp, Uall.data(), n * sizeof(float), hipMemcpyHostToDevice));
-        GEMHIP_CHECK(hipMemcpy(h->d_KTp, Kall.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-        GEMHIP_CHECK(hipMemcpy(h->d_UKp, UK.data(), n * sizeof(uint2), hipMemcpyHostToDevice));
-        GEMHIP_CHECK(hipMemcpy(h->d_KTslotp, Sdev.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+        GEMHIP_CHECK(h->d_UTp.upload(Uall.data(), n));
+        GEMHIP_CHECK(h->d_KTp.upload(Kall.data(), n));
+        GEMHIP_CHECK(h->d_UKp.upload(UK.data(), n));
+        GEMHIP_CHECK(h->d_KTslotp.upload(Sdev.data(), n));
     }
     h->parts = parts; h->skp_state = -1; h->parts_vocab_order = true;
-    hipFree(h->d_SKp); h->d_SKp = nullptr;
     if (UT_out) std::copy(Uall.begin(), Uall.end(), UT_out);
     if (KT_out) std::copy(Kall.begin(), Kall.end(), KT_out);
     if (slot_out) std::copy(Sall.begin(), Sall.end(), slot_out);
@@ -990,14 +957,9 @@ extern "C" int gemhip_sgns_init(gemhip_n2v_t h, int32_t d, uint64_t seed, void *
     GEMHIP_REQUIRE(h && d >= 1, "sgns_init: bad arguments");
     GEMHIP_REQUIRE(pick_sgns(d) != nullptr, "sgns_init: d=%d unsupported (even d <= 512, odd d <= 256)", d);
     GEMHIP_REQUIRE((dSynPos == nullptr) == (dSynNeg == nullptr), "sgns_init: pass both or neither external table");
-    if (h->own_syn) { hipFree(h->SynPos); hipFree(h->SynNeg); h->own_syn = false; }
-    const size_t bytes = (size_t)h->n * d * sizeof(float);
-    if (dSynPos) { h->SynPos = (float *)dSynPos; h->SynNeg = (float *)dSynNeg; }
-    else {
-        GEMHIP_CHECK(hipMalloc((void **)&h->SynPos, bytes));
-        GEMHIP_CHECK(hipMalloc((void **)&h->SynNeg, bytes));
-        h->own_syn = true;
-    }
+    h->syn_own[0].reset(); h->syn_own[1].reset(); h->SynPos = h->SynNeg = nullptr;
+    if (!dSynPos) for (auto &b : h->syn_own) GEMHIP_CHECK(b.reserve((size_t)h->n * d));
+    h->SynPos = dSynPos ? (float *)dSynPos : h->syn_own[0].get(); h->SynNeg = dSynPos ? (float *)dSynNeg : h->syn_own[1].get();
     h->d = d;
     const int64_t total = h->n * (int64_t)d;
     const int64_t threads = (total + 3) / 4;
@@ -1168,14 +1130,17 @@ static SgnsLaunchPlan plan_sgns_launch(const VocabStats &vs, const SgnsKnobs &kn
 // LOCALLY HOT ROWS: the array the Hogwild kernels compare with hot_thr -- the token count, or INT32_MAX for a node whose tokens are packed into few walks
 // (kernels above).  Built on `stream` from the walks this handle holds and its (possibly externally reduced) counts; rebuilt after walks / vocabulary
 // change.  n_local_hot is read back (one 4-byte copy): a launch without any such node and without count-hot rows keeps the all-cached instantiation.
+static int ensure_hotkey_buffers(gemhip_n2v_t h)
+{
+    GEMHIP_CHECK(h->d_hotkey.reserve(h->n));
+    GEMHIP_CHECK(h->d_wcount.reserve(h->n));
+    GEMHIP_CHECK(h->d_nlocal.reserve(1));
+    return GEMHIP_OK;
+}
 static int ensure_hotkey(gemhip_n2v_t h, hipStream_t stream)
 {
     if (h->hotkey_state == 1) return GEMHIP_OK;
-    if (!h->d_hotkey) {
-        GEMHIP_CHECK(hipMalloc((void **)&h->d_hotkey, (size_t)h->n * sizeof(int32_t)));
-        GEMHIP_CHECK(hipMalloc((void **)&h->d_wcount, (size_t)h->n * sizeof(int32_t)));
-        GEMHIP_CHECK(hipMalloc((void **)&h->d_nlocal, sizeof(unsigned int)));
-    }
+    if (int rc = ensure_hotkey_buffers(h)) return rc;
     GEMHIP_CHECK(hipMemsetAsync(h->d_wcount, 0, (size_t)h->n * sizeof(int32_t), stream));
     GEMHIP_CHECK(hipMemsetAsync(h->d_nlocal, 0, sizeof(unsigned int), stream));
     if (h->nwalks > 0) {
@@ -1197,11 +1162,7 @@ static int ensure_hotkey(gemhip_n2v_t h, hipStream_t stream)
 static int ensure_slot_table(gemhip_n2v_t h, const int32_t *KT, int64_t nslots, int quirk, hipStream_t stream)
 {
     if (h->sk_state == quirk && h->d_SK) return GEMHIP_OK;
-    if (nslots > h->sk_cap) {
-        if (h->d_SK) { GEMHIP_CHECK(hipDeviceSynchronize()); hipFree(h->d_SK); h->d_SK = nullptr; h->sk_cap = 0; }
-        GEMHIP_CHECK(hipMalloc((void **)&h->d_SK, (size_t)nslots * sizeof(uint4)));
-        h->sk_cap = nslots;
-    }
+    GEMHIP_CHECK(h->d_SK.reserve(nslots));
     hipLaunchKernelGGL(n2v_slot_table_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, stream, nslots, KT, h->d_UK, quirk, h->d_SK);
     GEMHIP_CHECK(hipGetLastError());
     h->sk_state = quirk;
@@ -1211,7 +1172,7 @@ static int ensure_slot_table(gemhip_n2v_t h, const int32_t *KT, int64_t nslots, 
 static int ensure_slot_table_parts(gemhip_n2v_t h, int quirk, hipStream_t stream)
 {
     if (h->skp_state == quirk && h->d_SKp) return GEMHIP_OK;
-    if (!h->d_SKp) GEMHIP_CHECK(hipMalloc((void **)&h->d_SKp, (size_t)h->n * sizeof(uint4)));
+    GEMHIP_CHECK(h->d_SKp.reserve(h->n));
     for (int32_t p = 0; p < h->parts; ++p) {
         const int64_t off = h->part_off[p], np = h->parts_vocab_order ? h->part_slots[p] : h->part_off[p + 1] - off;
         if (np <= 0) continue;
@@ -1221,6 +1182,21 @@ static int ensure_slot_table_parts(gemhip_n2v_t h, int quirk, hipStream_t stream
     }
     GEMHIP_CHECK(hipGetLastError());
     h->skp_state = quirk;
+    return GEMHIP_OK;
+}
+
+// The per-wavefront rows of the window kernels: one scratch row each (SgnsArgs::dummy, zeroed when it is allocated) and, for the delta write-back
+// of sgns_win_kernel<PART>, the 2R+1 window rows as loaded (SgnsArgs::scratch).  Grow-only: a launch that fits what is held makes no HIP call.
+static int ensure_win_scratch(gemhip_n2v_t h, const SgnsLaunchPlan &P, int32_t d, bool part_delta, SgnsArgs &A)
+{
+    const size_t need = (size_t)P.waves * sgns_win_row_floats(d);
+    if (need > h->d_dummy.capacity()) {
+        GEMHIP_CHECK(h->d_dummy.reserve(need));
+        GEMHIP_CHECK(hipMemset(h->d_dummy, 0, need * sizeof(float)));
+    }
+    A.dummy = h->d_dummy;
+    if (part_delta) GEMHIP_CHECK(h->d_scratch.reserve(need * (size_t)(2 * P.R + 1)));
+    A.scratch = part_delta ? h->d_scratch.get() : nullptr;
     return GEMHIP_OK;
 }
 
@@ -1268,14 +1244,7 @@ extern "C" int gemhip_sgns_train(gemhip_n2v_t h, int32_t window, int32_t neg, fl
         A.counts = h->d_counts; A.hot_thr = P.hot_thr;
         // LOCALLY HOT ROWS: the kernel compares `hotkey` (INT32_MAX for a node whose tokens are packed into few walks, else its token count) with the threshold
         if (P.delta && P.waves > 1 && kn_launch.has_local_hot) A.counts = h->d_hotkey;
-        const size_t need = (size_t)P.waves * sgns_win_row_floats(h->d) * sizeof(float);
-        if (need > h->dummy_bytes) {
-            if (h->d_dummy) { GEMHIP_CHECK(hipDeviceSynchronize()); hipFree(h->d_dummy); h->d_dummy = nullptr; h->dummy_bytes = 0; }
-            GEMHIP_CHECK(hipMalloc(&h->d_dummy, need));
-            GEMHIP_CHECK(hipMemset(h->d_dummy, 0, need));
-            h->dummy_bytes = need;
-        }
-        A.dummy = h->d_dummy;
+        { const int rc = ensure_win_scratch(h, P, h->d, false, A); if (rc) return rc; }
 #ifdef GEMHIP_SGNS_STALENESS
         static unsigned int *d_sver = nullptr; static unsigned long long *d_shist = nullptr; static int64_t sver_n = 0;
         if (sver_n < h->n) { if (d_sver) hipFree(d_sver); GEMHIP_CHECK(hipMalloc(&d_sver, (size_t)h->n * 2 * sizeof(unsigned int))); sver_n = h->n; }
@@ -1414,24 +1383,7 @@ extern "C" int gemhip_sgns_train_part(gemhip_n2v_t h, const void *d_walks, int64
     GEMHIP_REQUIRE(P.window, "sgns_train_part: d=%d window=%d walk_len=%d do not fit the LDS window kernel", d, window, walk_len);
     A.nwaves = (int32_t)P.waves; A.cache_radius = P.R; A.hot_thr = P.hot_thr;
     if (kn.has_local_hot && P.delta && P.waves > 1) A.counts = h->d_hotkey;
-    const size_t need = (size_t)P.waves * sgns_win_row_floats(d) * sizeof(float);
-    if (need > h->dummy_bytes) {
-        if (h->d_dummy) { GEMHIP_CHECK(hipDeviceSynchronize()); hipFree(h->d_dummy); h->d_dummy = nullptr; h->dummy_bytes = 0; }
-        GEMHIP_CHECK(hipMalloc(&h->d_dummy, need));
-        GEMHIP_CHECK(hipMemset(h->d_dummy, 0, need));
-        h->dummy_bytes = need;
-    }
-    A.dummy = h->d_dummy;
-    A.scratch = nullptr;
-    if (P.delta) {
-        const size_t sneed = (size_t)P.waves * (size_t)(2 * P.R + 1) * sgns_win_row_floats(d) * sizeof(float);
-        if (sneed > h->scratch_bytes) {
-            if (h->d_scratch) { GEMHIP_CHECK(hipDeviceSynchronize()); hipFree(h->d_scratch); h->d_scratch = nullptr; h->scratch_bytes = 0; }
-            GEMHIP_CHECK(hipMalloc(&h->d_scratch, sneed));
-            h->scratch_bytes = sneed;
-        }
-        A.scratch = h->d_scratch;
-    }
+    { const int rc = ensure_win_scratch(h, P, d, P.delta, A); if (rc) return rc; }
     sgns_fn fn = pick_sgns_win_part(d, P.delta);
     GEMHIP_REQUIRE(fn != nullptr, "sgns_train_part: d=%d unsupported", d);
     h->last_plan = P; h->last_fresh = (P.delta && P.hot_thr > 0) ? A.fresh : 0;
@@ -1465,12 +1417,11 @@ __global__ void wave_sum6_test_kernel(const float *in, float *out)
 extern "C" int gemhip_test_wave_sum6(const float *in_host, float *out_host)
 {
     GEMHIP_REQUIRE(in_host && out_host, "test_wave_sum6: NULL argument");
-    float *d = nullptr;
-    GEMHIP_CHECK(hipMalloc(&d, (64 * 6 + 64) * sizeof(float)));
+    DevBuf<float> d;
+    GEMHIP_CHECK(d.reserve(64 * 6 + 64));
     hipError_t e = hipMemcpy(d, in_host, 64 * 6 * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) { hipLaunchKernelGGL(wave_sum6_test_kernel, dim3(1), dim3(64), 0, 0, d, d + 64 * 6); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpy(out_host, d + 64 * 6, 64 * sizeof(float), hipMemcpyDeviceToHost);
-    hipFree(d);
     if (e != hipSuccess) return fail(GEMHIP_E_HIP, "test_wave_sum6: %s", hipGetErrorString(e));
     return GEMHIP_OK;
 }
@@ -1500,11 +1451,7 @@ extern "C" int gemhip_n2v_locally_hot_corpus(gemhip_n2v_t h, const void *d_corpu
     h->hotkey_state = 0; h->n_local_hot = 0;
     if (h->kn.local_hot == 0) { if (count) *count = 0; return GEMHIP_OK; }
     hipStream_t s = (hipStream_t)stream;
-    if (!h->d_hotkey) {
-        GEMHIP_CHECK(hipMalloc((void **)&h->d_hotkey, (size_t)h->n * sizeof(int32_t)));
-        GEMHIP_CHECK(hipMalloc((void **)&h->d_wcount, (size_t)h->n * sizeof(int32_t)));
-        GEMHIP_CHECK(hipMalloc((void **)&h->d_nlocal, sizeof(unsigned int)));
-    }
+    if (int rc = ensure_hotkey_buffers(h)) return rc;
     GEMHIP_CHECK(hipMemsetAsync(h->d_wcount, 0, (size_t)h->n * sizeof(int32_t), s));
     GEMHIP_CHECK(hipMemsetAsync(h->d_nlocal, 0, sizeof(unsigned int), s));
     hipLaunchKernelGGL(n2v_walk_presence_kernel, dim3((unsigned)std::min<int64_t>(corpus_rows, 256 * 32)), dim3(64), (size_t)walk_len * sizeof(int32_t), s, (const int32_t *)d_corpus,

@@ -9,9 +9,10 @@
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p gem_amd/build/asan
-for f in eval gf hope runtime n2v sgns_hogwild sgns_det sgns_part multi; do
+rm -f gem_amd/build/asan/*.o
+for src in gem_amd/csrc/*.hip; do          # every source the library is built from (gem_amd.build.sources() takes the same glob)
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=address -fno-gpu-sanitize -fno-omit-frame-pointer -w \
-        -c gem_amd/csrc/$f.hip -o gem_amd/build/asan/$f.hip.o &
+        -c "$src" -o "gem_amd/build/asan/$(basename "$src").o" &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address -o gem_amd/libgem_hip_asan.so gem_amd/build/asan/*.o -ldl
