@@ -76,6 +76,23 @@ _SIGS = {
     'gemhip_hope_spmm': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_float, C.c_int32, f32p, f32p, f32p]),
     'gemhip_hope_gram': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, f32p, f64p]),
     'gemhip_hope_tsgemm': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, f64p, C.c_float, f32p, f32p]),
+    # test hooks: HOPE's host functions under the solvers' calling conventions (include/gem_hip.h, "test hooks")
+    'gemhip_test_hope_spmm': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_float, C.c_int32, f32p, C.c_int32, C.c_float, f32p, C.c_int32,
+                                        C.c_float, f32p, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int32, i32p]),
+    'gemhip_test_hope_gram': (C.c_int, [C.c_int64, f32p, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32, f64p, f32p]),
+    'gemhip_test_hope_gram2': (C.c_int, [C.c_int64, f32p, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32, f64p,
+                                         f32p, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32, f64p]),
+    'gemhip_test_hope_tsgemm': (C.c_int, [C.c_int64, f32p, C.c_int32, C.c_int32, C.c_int32, f64p, C.c_int32, C.c_float, f32p, C.c_int32, C.c_int32, f32p,
+                                          C.c_int32]),
+    'gemhip_test_hope_ritz': (C.c_int, [C.c_int64, f32p, C.c_int32, C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32, f64p, f64p, C.c_int32, f32p, C.c_int32,
+                                        f64p]),
+    'gemhip_test_hope_colmax': (C.c_int, [C.c_int64, f32p, C.c_int32, C.c_int32, C.c_int32, f32p]),
+    'gemhip_test_hope_project_out': (C.c_int, [C.c_int64, f32p, C.c_int32, C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32]),
+    'gemhip_test_hope_sym_op': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_float, f32p, C.c_int32, C.c_int32, C.c_float, f32p, C.c_int32,
+                                          C.c_float, f32p, C.c_int32, f32p, C.c_int32]),
+    'gemhip_test_hope_lincomb': (C.c_int, [C.c_int64, C.c_int32, C.c_float, f32p, C.c_int32, C.c_float, f32p, C.c_int32, C.c_float, f32p, C.c_int32, C.c_int32,
+                                           f32p, C.c_int32]),
+    'gemhip_test_hope_randn': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_uint64, f32p]),
     'gemhip_eval_sampled_ap': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, f32p, i64p, i32p, C.c_int32, C.c_int64, i32p, f64p]),
     'gemhip_n2v_train': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_uint64, C.c_int32, f32p, f64p]),

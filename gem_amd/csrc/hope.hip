@@ -84,7 +84,9 @@ __global__ __launch_bounds__(256) void hope_spmm_kernel(int64_t n, const int64_t
 // Quarter-wave variant for blocks of up to 128 columns: 16 lanes per row, four rows per wavefront.  The one-row-per-wavefront kernel
 // above is bound by its dependent chain (row_ptr -> col/val -> gathers -> store: ~12 rounds of resident waves at n = 100k, each a few
 // microseconds) and leaves the lanes beyond b idle; four independent chains per wavefront cut the rounds by four.  Lane l of a group
-// owns columns l, l+16, ...: a neighbour's row is read as CPL16 64-byte segments.  Neighbours are added in edge order like above.
+// owns columns l, l+16, ...: a neighbour's row is read as CPL16 64-byte segments.  Neighbours are added in edge order like above: the same order,
+// not the same bits -- the compiler fuses the kernel above's multiply-adds and compiles this one's to packed multiplies and adds, so the two
+// agree to rounding, while every U of this kernel gives the same bits (tests/test_hope_blocks_gpu.py::test_spmm_variants_are_bit_identical).
 template <int CPL16, int U>
 __global__ __launch_bounds__(256) void hope_spmm16_kernel(int64_t n, const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
                                                           const float *__restrict__ val, float alpha, const float *__restrict__ X, int ldx,
@@ -1201,6 +1203,11 @@ struct Hope {
     CoefSlot coef[8]; unsigned coef_next = 0;                // pinned staging ring for the small host matrices tsgemm() takes
     DevBuf<float> ws[7];                                     // eigen-path workspace, kept across solves
     DevBuf<float> d_cm;                                      // 512 floats: column arg-max signs of the output step
+    // Kernel-variant overrides (the gemhip_test_hope_* hooks set them; -1 = unset: the environment variable, else the default, decides)
+    int force_spmm16 = -1;                                   // GEMHIP_HOPE_SPMM16: 0 = one row per wavefront, 1 = 16 lanes per row up to 128 columns
+    int force_spmm16_u = -1;                                 // GEMHIP_HOPE_SPMM16_U: gathers in flight per row and round (2, 4, 8)
+    int force_colmax2 = -1;                                  // GEMHIP_HOPE_COLMAX2: 0 = one block per column, 1 = two coalesced passes
+    int last_spmm_c = 0, last_spmm_u = 0;                    // the instantiation spmm() launched last: <CPL16, U>, or <CPL> with U = 0 (the hooks report it)
     int err = 0;
     ~Hope()          // the events; the buffers free themselves
     {
@@ -1218,17 +1225,18 @@ void spmm(Hope &H, bool transpose, float alpha, const float *X, int ldx, const f
     const int64_t blocks = (H.n + 3) / 4;
     const dim3 grid((unsigned)((blocks + NUM_XCD - 1) / NUM_XCD * NUM_XCD)), blk(256);
     const int64_t *rp = transpose ? H.rpT : H.rp; const int32_t *ci = transpose ? H.ciT : H.ci; const float *va = transpose ? H.vaT : H.va;
-    static const int use16 = getenv("GEMHIP_HOPE_SPMM16") ? atoi(getenv("GEMHIP_HOPE_SPMM16")) : 1;
+    static const int use16_env = getenv("GEMHIP_HOPE_SPMM16") ? atoi(getenv("GEMHIP_HOPE_SPMM16")) : 1;
+    const int use16 = H.force_spmm16 >= 0 ? H.force_spmm16 : use16_env;
     if (use16 && b <= 128) {
         const int64_t blocks16 = (H.n + 15) / 16;
         const dim3 grid16((unsigned)((blocks16 + NUM_XCD - 1) / NUM_XCD * NUM_XCD));
         const int c16 = (b + 15) / 16;
-#define SPMM16(C, U) hipLaunchKernelGGL((hope_spmm16_kernel<C, U>), grid16, blk, 0, H.s, H.n, rp, ci, va, alpha, X, ldx, Wadd, ldw, Y, ldy, b, wa, W2, ldw2, wb)
+#define SPMM16(C, U) do { H.last_spmm_c = C; H.last_spmm_u = U; hipLaunchKernelGGL((hope_spmm16_kernel<C, U>), grid16, blk, 0, H.s, H.n, rp, ci, va, alpha, X, ldx, Wadd, ldw, Y, ldy, b, wa, W2, ldw2, wb); } while (0)
         // gathers in flight per row and round (GEMHIP_HOPE_SPMM16_U overrides): with a row's (column, value) pairs already in the group's registers the
         // rounds are separated by arithmetic only, and the bound is registers: U x ceil(b / 16) values per lane -- 8 up to 48 columns, 4 up to 80, 2 beyond
         // (round 5: 4.21 -> 3.92 ms of SpMM per eigen-path solve at SBM 100k/1M against round 4's U = 4 with a per-round pair prefetch)
         static const int uenv = getenv("GEMHIP_HOPE_SPMM16_U") ? atoi(getenv("GEMHIP_HOPE_SPMM16_U")) : 0;
-        const int uu = uenv > 0 ? uenv : (c16 <= 3 ? 8 : 4);
+        const int uu = H.force_spmm16_u > 0 ? H.force_spmm16_u : uenv > 0 ? uenv : (c16 <= 3 ? 8 : 4);
 #define SPMM16_BY_U(C) do { if (uu >= 8) SPMM16(C, 8); else if (uu >= 4) SPMM16(C, 4); else SPMM16(C, 2); } while (0)
         if (c16 <= 1) SPMM16_BY_U(1);
         else if (c16 <= 2) SPMM16_BY_U(2);
@@ -1243,7 +1251,7 @@ void spmm(Hope &H, bool transpose, float alpha, const float *X, int ldx, const f
         return;
     }
     const int cpl = (b + 63) / 64;
-#define SPMM(C) hipLaunchKernelGGL((hope_spmm_kernel<C>), grid, blk, 0, H.s, H.n, rp, ci, va, alpha, X, ldx, Wadd, ldw, Y, ldy, b, wa, W2, ldw2, wb)
+#define SPMM(C) do { H.last_spmm_c = C; H.last_spmm_u = 0; hipLaunchKernelGGL((hope_spmm_kernel<C>), grid, blk, 0, H.s, H.n, rp, ci, va, alpha, X, ldx, Wadd, ldw, Y, ldy, b, wa, W2, ldw2, wb); } while (0)
     if (cpl <= 1) SPMM(1); else if (cpl <= 2) SPMM(2); else if (cpl <= 4) SPMM(4); else SPMM(8);
 #undef SPMM
     H.spmm_count += 1; H.spmm_cols += b;
@@ -1365,7 +1373,8 @@ void ritz_rotate(Hope &H, const float *V, int ldv, const float *B, int ldb, int 
 void colmax(Hope &H, const float *X, int ld, int mc, float *val)
 {
     if (H.err || mc <= 0) return;
-    static const int two_pass = getenv("GEMHIP_HOPE_COLMAX2") ? atoi(getenv("GEMHIP_HOPE_COLMAX2")) : 1;
+    static const int two_pass_env = getenv("GEMHIP_HOPE_COLMAX2") ? atoi(getenv("GEMHIP_HOPE_COLMAX2")) : 1;
+    const int two_pass = H.force_colmax2 >= 0 ? H.force_colmax2 : two_pass_env;
     if (!two_pass) { hipLaunchKernelGGL(hope_colmax_kernel, dim3(mc), dim3(256), 0, H.s, H.n, X, ld, val); return; }
     const int nchunks = (int)std::min<int64_t>(512, (H.n + 63) / 64);
     const int64_t rows_per_chunk = (H.n + nchunks - 1) / nchunks;
@@ -1390,6 +1399,21 @@ void project_out(Hope &H, const float *V, int ldv, int m, float *W, int ldw, int
     gram_launch(H, V, ldv, m, W, ldw, cols, H.Csmall);
     if (H.err) return;
     tsgemm_launch(H, V, ldv, m, H.Csmall, cols, -1.0f, W, ldw, W, ldw);
+}
+
+// Out[:, :b] = a X + b2 Y + c Z over the H.n rows (hope_lincomb_kernel; Out may be one of the operands: every element is read, then written, by one thread)
+void lincomb(Hope &H, int b, float a, const float *X, int ldx, float b2, const float *Y, int ldy, float c, const float *Z, int ldz, float *Out, int ldo)
+{
+    if (H.err) return;
+    hipLaunchKernelGGL(hope_lincomb_kernel, dim3((unsigned)((H.n * b + 255) / 256)), dim3(256), 0, H.s, H.n, b, a, X, ldx, b2, Y, ldy, c, Z, ldz, Out, ldo);
+}
+
+// X[:, :b] = standard normal draws, a function of (seed, row, column, b) alone (hope_randn_kernel: four values per thread)
+void randn(Hope &H, float *X, int b, int ld, uint64_t seed)
+{
+    if (H.err) return;
+    const int64_t threads = (H.n * (int64_t)b + 3) / 4;
+    hipLaunchKernelGGL(hope_randn_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, H.s, X, H.n, b, ld, seed);
 }
 
 // Upper-triangular Cholesky G = R^T R in fp64 with a pivot floor; on success C = R^-1 (so that (Y C)^T (Y C) = I).
@@ -1488,9 +1512,7 @@ void apply_S(Hope &H, const float *X, int ldx, int b, int terms, float *T0, floa
     if (H.mode == 2) {                                                                         // c X - N^T N X,  N = I - P
         spmm(H, false, -1.0f, X, ldx, X, ldx, W0, ldt, b);                                     // W0 = N X = X - P X
         spmm(H, true, 1.0f, W0, ldt, nullptr, 0, T0, ldt, b);                                  // T0 = P^T W0
-        if (!H.err)
-            hipLaunchKernelGGL(hope_lincomb_kernel, dim3((unsigned)((H.n * b + 255) / 256)), dim3(256), 0, H.s, H.n, b, H.beta, X, ldx, -1.0f, W0, ldt, 1.0f,
-                               T0, ldt, Out, ldo);                                             // c X - W0 + P^T W0
+        lincomb(H, b, H.beta, X, ldx, -1.0f, W0, ldt, 1.0f, T0, ldt, Out, ldo);                 // c X - W0 + P^T W0
         return;
     }
     spmm(H, false, H.beta, X, ldx, nullptr, 0, W0, ldt, b);
@@ -1517,9 +1539,7 @@ void apply_ST(Hope &H, const float *Y, int ldy, int b, int terms, float *T0, flo
     if (H.mode == 2) {                                                                         // symmetric: same as apply_S (T0, T1 as scratch)
         spmm(H, false, -1.0f, Y, ldy, Y, ldy, T1, ldt, b);
         spmm(H, true, 1.0f, T1, ldt, nullptr, 0, T0, ldt, b);
-        if (!H.err)
-            hipLaunchKernelGGL(hope_lincomb_kernel, dim3((unsigned)((H.n * b + 255) / 256)), dim3(256), 0, H.s, H.n, b, H.beta, Y, ldy, -1.0f, T1, ldt, 1.0f,
-                               T0, ldt, Out, ldo);
+        lincomb(H, b, H.beta, Y, ldy, -1.0f, T1, ldt, 1.0f, T0, ldt, Out, ldo);
         return;
     }
     const float *rin = Y; int ldr = ldy;
@@ -1563,8 +1583,7 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
     if (H.err) { drop_events(); return H.err; }
     hipEventRecord(ev0, H.s);
 
-    const int64_t threads = (n * (int64_t)b + 3) / 4;
-    hipLaunchKernelGGL(hope_randn_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, H.s, Vall, n, b, ldm, seed);
+    randn(H, Vall, b, ldm, seed);
     int m0 = orth(H, Vall, ldm, b, Tmp, ldm, 1e-10);
 
     // Locking (deflation): a leading Ritz pair of the restart block whose residual ||S^T S v - sigma^2 v|| / sigma^2 fell
@@ -1805,8 +1824,7 @@ void apply_sym_op(Hope &H, int kind, float alpha, const float *X, int ldx, int c
     if (!W && !W2) { spmm(H, true, -alpha, T, ldt, T, ldt, Out, ldo, cols, alpha); return; }     // alpha (T - P^T T)
     // alpha (T - P^T T) + wa W + wb W2: the SpMM epilogue takes two addends, so W and W2 are combined first (into Out, which the
     // epilogue then reads and overwrites element by element)
-    hipLaunchKernelGGL(hope_lincomb_kernel, dim3((unsigned)((H.n * cols + 255) / 256)), dim3(256), 0, H.s, H.n, cols, W ? wa : 0.f, W ? W : T, W ? ldw : ldt,
-                       W2 ? wb : 0.f, W2 ? W2 : T, W2 ? ldw2 : ldt, 0.f, T, ldt, Out, ldo);
+    lincomb(H, cols, W ? wa : 0.f, W ? W : T, W ? ldw : ldt, W2 ? wb : 0.f, W2 ? W2 : T, W2 ? ldw2 : ldt, 0.f, T, ldt, Out, ldo);
     spmm(H, true, -alpha, T, ldt, T, ldt, Out, ldo, cols, alpha, Out, ldo, 1.0f);
 }
 
@@ -1892,8 +1910,7 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
     hipEventRecord(ev0, H.s);
     const auto ht1 = std::chrono::steady_clock::now();
 
-    const int64_t threads = (n * (int64_t)b + 3) / 4;
-    hipLaunchKernelGGL(hope_randn_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, H.s, Vall, n, b, ldv, seed);
+    randn(H, Vall, b, ldv, seed);
     int ma = orth_scaled(H, Vall, ldv, b, Tmp, ldv, 1), nl = 0;      // (one CholeskyQR pass: a Gaussian block is well conditioned, and the first filter is followed by the full CholeskyQR2)
 
     const double L = kind == 1 ? 1.0001 : kind == 2 ? beta : br / std::fabs(beta);   // |lambda| <= L: power-iteration estimate + margin
@@ -2207,8 +2224,7 @@ static int hope_setup(gemhip_hope_plan &P, int64_t n, int64_t nnz, const int64_t
             if (!(nz > 0.0) || !(nx > 0.0) || !std::isfinite(nz)) break;
             const double prev = rho;
             rho = std::sqrt(std::sqrt(nz / nx));
-            hipLaunchKernelGGL(hope_lincomb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, H.s, n, 1, (float)(1.0 / std::sqrt(nz)), X2 + 1, 2, 0.f, X2 + 1, 2,
-                               0.f, X2 + 1, 2, X2, 2);                               // x = z / |z|
+            lincomb(H, 1, (float)(1.0 / std::sqrt(nz)), X2 + 1, 2, 0.f, X2 + 1, 2, 0.f, X2 + 1, 2, X2, 2);      // x = z / |z|
             if (it >= 4 && std::fabs(rho - prev) <= 1e-3 * rho) break;                // the 10 % margin below covers the rest
         }
         HOPE_TRY(H, hipStreamSynchronize(H.s));
@@ -2353,7 +2369,7 @@ static int svd_error_impl(gemhip_hope_plan_t P, int32_t k, const float *sigma, c
             spmm(H, false, H.beta, dV + c0, ldv, nullptr, 0, dBV + c0, ldv, cb);
         }
         gram(H, dBV, ldv, k, dBV, ldv, k, Gbv);
-        hipLaunchKernelGGL(hope_randn_kernel, dim3((unsigned)((n * probes / 4 + 256) / 256)), dim3(256), 0, H.s, blk[0], n, probes, ld, seed ^ 0x5356444572726F72ull);
+        randn(H, blk[0], probes, ld, seed ^ 0x5356444572726F72ull);
         gram(H, dV, ldv, k, blk[0], ld, probes, C);                            // V^T Z  (k x probes)
         tsgemm(H, dV, ldv, k, C, probes, -1.0f, blk[0], ld, blk[0], ld);       // Z <- Z - V (V^T Z)
         apply_S(H, blk[0], ld, probes, P->terms, blk[1], blk[2], blk[3], ld, blk[4], ld);           // W0 keeps the first term B Z
@@ -2375,9 +2391,7 @@ static int svd_error_impl(gemhip_hope_plan_t P, int32_t k, const float *sigma, c
             HOPE_TRY(H, hipMemcpyAsync(cb[4], Uh.data(), Uh.size() * sizeof(float), hipMemcpyHostToDevice, H.s));
             HOPE_TRY(H, hipMemsetAsync(cb[3], 0, (size_t)n * ldc * sizeof(float), H.s));
             apply_S(H, dV + c0, ldv, cbn, P->terms, cb[0], cb[1], cb[2], ldc, cb[3], ldc);
-            if (!H.err)
-                hipLaunchKernelGGL(hope_lincomb_kernel, dim3((unsigned)((n * ldc + 255) / 256)), dim3(256), 0, H.s, n, ldc, 1.0f, cb[3], ldc, -1.0f, cb[4], ldc, 0.0f,
-                                   cb[4], ldc, cb[4], ldc);                 // residual in place (padding columns: 0 - 0)
+            lincomb(H, ldc, 1.0f, cb[3], ldc, -1.0f, cb[4], ldc, 0.0f, cb[4], ldc, cb[4], ldc);      // residual in place (padding columns: 0 - 0)
             std::vector<double> Gr;
             const int cpad = (cbn + 31) / 32 * 32;
             gram(H, cb[4], ldc, cpad, cb[4], ldc, cpad, Gr);
@@ -2547,8 +2561,7 @@ extern "C" int gemhip_lle(int64_t n, int64_t nnz, const int64_t *row_ptr, const 
             if (!(nz > 0.0) || !(nx > 0.0) || !std::isfinite(nz)) break;
             const double prev = est;
             est = std::sqrt(nz / nx);
-            hipLaunchKernelGGL(hope_lincomb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, H.s, n, 1, (float)(1.0 / std::sqrt(nz)), X2 + 1, 2, 0.f, X2 + 1, 2,
-                               0.f, X2 + 1, 2, X2, 2);                                                    // x = z / |z|
+            lincomb(H, 1, (float)(1.0 / std::sqrt(nz)), X2 + 1, 2, 0.f, X2 + 1, 2, 0.f, X2 + 1, 2, X2, 2);      // x = z / |z|
             if (it >= 8 && std::fabs(est - prev) <= 1e-4 * est) break;                                     // the 5 % margin covers the rest
         }
         HOPE_TRY(H, hipStreamSynchronize(H.s));
@@ -2668,4 +2681,222 @@ extern "C" int gemhip_hope_tsgemm(int64_t n, int32_t m, int32_t b2, const float 
     tsgemm(H, dX, m, m, C, b2, alpha, dS, b2, dO, b2);
     HOPE_TRY(H, hipMemcpy(Out_host, dO, (size_t)n * b2 * 4, hipMemcpyDeviceToHost));
     return H.err;
+}
+
+// ------------------------------------------------------------------ test hooks: the host functions above, under the solvers' calling conventions
+// Each hook uploads host blocks (every one with its full leading dimension, padding included), calls the host function the solvers call on a local
+// Hope, and copies the output block back whole, so a caller that filled the padding with a sentinel sees any write outside the logical columns.
+namespace {
+
+// A (CSR, n x n) and its transpose on the device, the transpose by the counting sort of hope_setup / gemhip_lle (values default to 1)
+void hook_upload_csr(Hope &H, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, bool with_transpose)
+{
+    H.n = n; H.nnz = nnz;
+    std::vector<float> va(std::max<int64_t>(nnz, 1), 1.0f);
+    if (w) std::copy(w, w + nnz, va.begin());
+    HOPE_TRY(H, H.rp.upload(row_ptr, n + 1)); HOPE_TRY(H, H.ci.upload(col, nnz)); HOPE_TRY(H, H.va.upload(va.data(), nnz));
+    if (!with_transpose) return;
+    std::vector<int64_t> rpT(n + 1, 0);
+    std::vector<int32_t> ciT(std::max<int64_t>(nnz, 1));
+    std::vector<float> vaT(std::max<int64_t>(nnz, 1));
+    for (int64_t e = 0; e < nnz; ++e) ++rpT[col[e] + 1];
+    for (int64_t i = 0; i < n; ++i) rpT[i + 1] += rpT[i];
+    std::vector<int64_t> at(rpT.begin(), rpT.end() - 1);
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) { const int64_t q = at[col[e]]++; ciT[q] = (int32_t)i; vaT[q] = va[e]; }
+    HOPE_TRY(H, H.rpT.upload(rpT.data(), n + 1)); HOPE_TRY(H, H.ciT.upload(ciT.data(), nnz)); HOPE_TRY(H, H.vaT.upload(vaT.data(), nnz));
+}
+
+bool hook_csr_ok(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col)
+{
+    if (n < 1 || nnz < 0 || !row_ptr || (nnz > 0 && !col) || row_ptr[0] != 0 || row_ptr[n] != nnz) return false;
+    for (int64_t i = 0; i < n; ++i) if (row_ptr[i + 1] < row_ptr[i]) return false;
+    for (int64_t e = 0; e < nnz; ++e) if (col[e] < 0 || col[e] >= n) return false;
+    return true;
+}
+
+int hook_download(Hope &H, void *host, const void *dev, size_t bytes)      // blocking: the null stream's work is done when it returns
+{
+    HOPE_TRY(H, hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+    return H.err;
+}
+
+}  // namespace
+
+// variant: 0 = the production dispatch, 1 = hope_spmm_kernel (one row per wavefront), 2 / 4 / 8 = hope_spmm16_kernel with that U.
+// w_is_x: Wadd is the device block of X itself (ldw = ldx); w2_is_y: W2 is the device block of Y itself (Y_inout's contents, ldw2 = ldy).
+// launched_out (may be NULL): the instantiation spmm() chose, {CPL16, U} or {CPL, 0}.
+extern "C" int gemhip_test_hope_spmm(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t variant, float alpha,
+                                     int32_t b, const float *X_host, int32_t ldx, float wa, const float *W_host, int32_t ldw, float wb,
+                                     const float *W2_host, int32_t ldw2, int32_t w_is_x, int32_t w2_is_y, float *Y_inout, int32_t ldy,
+                                     int32_t *launched_out)
+{
+    GEMHIP_REQUIRE(hook_csr_ok(n, nnz, row_ptr, col), "test_hope_spmm: bad CSR arguments");
+    GEMHIP_REQUIRE(X_host && Y_inout && b >= 1 && b <= 512 && ldx >= b && ldy >= b, "test_hope_spmm: bad block arguments");
+    GEMHIP_REQUIRE(variant == 0 || variant == 1 || ((variant == 2 || variant == 4 || variant == 8) && b <= 128), "test_hope_spmm: variant %d", variant);
+    GEMHIP_REQUIRE(!(w_is_x && W_host) && !(w2_is_y && W2_host) && (!W_host || ldw >= b) && (!W2_host || ldw2 >= b), "test_hope_spmm: bad addend arguments");
+    Hope H;
+    hook_upload_csr(H, n, nnz, row_ptr, col, w, false);
+    if (variant == 1) H.force_spmm16 = 0;
+    if (variant >= 2) { H.force_spmm16 = 1; H.force_spmm16_u = variant; }
+    DevBuf<float> dX, dW, dW2, dY;
+    HOPE_TRY(H, dX.upload(X_host, (size_t)n * ldx));
+    if (W_host) HOPE_TRY(H, dW.upload(W_host, (size_t)n * ldw));
+    if (W2_host) HOPE_TRY(H, dW2.upload(W2_host, (size_t)n * ldw2));
+    HOPE_TRY(H, dY.upload(Y_inout, (size_t)n * ldy));
+    const float *pW = w_is_x ? dX.get() : dW.get(); const int lw = w_is_x ? ldx : ldw;
+    const float *pW2 = w2_is_y ? dY.get() : dW2.get(); const int lw2 = w2_is_y ? ldy : ldw2;
+    spmm(H, false, alpha, dX, ldx, pW, lw, dY, ldy, b, wa, pW2, lw2, wb);
+    if (launched_out) { launched_out[0] = H.last_spmm_c; launched_out[1] = H.last_spmm_u; }
+    return hook_download(H, Y_inout, dY, (size_t)n * ldy * sizeof(float));
+}
+
+// G[m1][m2] = X[:, xoff : xoff + m1]^T Y[:, yoff : yoff + m2]; Y_host NULL: Y is the device block of X (ldy = ldx).  Gf_host (may be NULL) receives
+// the fp32 rounding hope_reduce2_kernel writes for project_out.
+extern "C" int gemhip_test_hope_gram(int64_t n, const float *X_host, int32_t ldx, int32_t xoff, int32_t m1, const float *Y_host, int32_t ldy, int32_t yoff,
+                                     int32_t m2, double *G_host, float *Gf_host)
+{
+    GEMHIP_REQUIRE(n >= 1 && X_host && G_host && m1 >= 1 && m2 >= 1 && xoff >= 0 && yoff >= 0 && xoff + m1 <= ldx && yoff + m2 <= (Y_host ? ldy : ldx),
+                   "test_hope_gram: bad arguments");
+    Hope H; H.n = n;
+    DevBuf<float> dX, dY, dGf;
+    HOPE_TRY(H, dX.upload(X_host, (size_t)n * ldx));
+    if (Y_host) HOPE_TRY(H, dY.upload(Y_host, (size_t)n * ldy));
+    const float *pY = Y_host ? dY.get() : dX.get(); const int ly = Y_host ? ldy : ldx;
+    if (!Gf_host) {
+        std::vector<double> G;
+        gram(H, dX + xoff, ldx, m1, pY + yoff, ly, m2, G);
+        if (!H.err) std::copy(G.begin(), G.end(), G_host);
+        return H.err;
+    }
+    HOPE_TRY(H, dGf.reserve((size_t)m1 * m2));
+    gram_launch(H, dX + xoff, ldx, m1, pY + yoff, ly, m2, dGf);
+    if (hook_download(H, G_host, H.G, (size_t)m1 * m2 * sizeof(double))) return H.err;
+    return hook_download(H, Gf_host, dGf, (size_t)m1 * m2 * sizeof(float));
+}
+
+// gram2: Ga = Xa[:, xaoff : +ma1]^T Ya[:, yaoff : +ma2] and Gb likewise, in one call (shared scratch, one host round trip)
+extern "C" int gemhip_test_hope_gram2(int64_t n, const float *Xa_host, int32_t ldxa, int32_t xaoff, int32_t ma1, const float *Ya_host, int32_t ldya,
+                                      int32_t yaoff, int32_t ma2, double *Ga_host, const float *Xb_host, int32_t ldxb, int32_t xboff, int32_t mb1,
+                                      const float *Yb_host, int32_t ldyb, int32_t yboff, int32_t mb2, double *Gb_host)
+{
+    GEMHIP_REQUIRE(n >= 1 && Xa_host && Ya_host && Xb_host && Yb_host && Ga_host && Gb_host, "test_hope_gram2: NULL argument");
+    GEMHIP_REQUIRE(ma1 >= 1 && ma2 >= 1 && mb1 >= 1 && mb2 >= 1 && xaoff >= 0 && yaoff >= 0 && xboff >= 0 && yboff >= 0 && xaoff + ma1 <= ldxa &&
+                   yaoff + ma2 <= ldya && xboff + mb1 <= ldxb && yboff + mb2 <= ldyb, "test_hope_gram2: bad shapes");
+    Hope H; H.n = n;
+    DevBuf<float> dXa, dYa, dXb, dYb;
+    HOPE_TRY(H, dXa.upload(Xa_host, (size_t)n * ldxa)); HOPE_TRY(H, dYa.upload(Ya_host, (size_t)n * ldya));
+    HOPE_TRY(H, dXb.upload(Xb_host, (size_t)n * ldxb)); HOPE_TRY(H, dYb.upload(Yb_host, (size_t)n * ldyb));
+    std::vector<double> Ga, Gb;
+    gram2(H, dXa + xaoff, ldxa, ma1, dYa + yaoff, ldya, ma2, Ga, dXb + xboff, ldxb, mb1, dYb + yboff, ldyb, mb2, Gb);
+    if (!H.err) { std::copy(Ga.begin(), Ga.end(), Ga_host); std::copy(Gb.begin(), Gb.end(), Gb_host); }
+    return H.err;
+}
+
+// Out[:, :b2] = (Src or 0) + alpha X[:, xoff : xoff + m] C.  in_place: Src is the device block of Out (Out_inout's contents, lds = ldo).
+extern "C" int gemhip_test_hope_tsgemm(int64_t n, const float *X_host, int32_t ldx, int32_t xoff, int32_t m, const double *C_host, int32_t b2, float alpha,
+                                       const float *Src_host, int32_t lds, int32_t in_place, float *Out_inout, int32_t ldo)
+{
+    GEMHIP_REQUIRE(n >= 1 && m >= 1 && b2 >= 1 && X_host && C_host && Out_inout && xoff >= 0 && xoff + m <= ldx && ldo >= b2, "test_hope_tsgemm: bad arguments");
+    GEMHIP_REQUIRE(!(in_place && Src_host) && (!Src_host || lds >= b2), "test_hope_tsgemm: bad Src arguments");
+    Hope H; H.n = n;
+    DevBuf<float> dX, dS, dO;
+    HOPE_TRY(H, dX.upload(X_host, (size_t)n * ldx));
+    if (Src_host) HOPE_TRY(H, dS.upload(Src_host, (size_t)n * lds));
+    HOPE_TRY(H, dO.upload(Out_inout, (size_t)n * ldo));
+    std::vector<double> C(C_host, C_host + (size_t)m * b2);
+    tsgemm(H, dX + xoff, ldx, m, C, b2, alpha, in_place ? dO.get() : dS.get(), in_place ? ldo : lds, dO, ldo);
+    return hook_download(H, Out_inout, dO, (size_t)n * ldo * sizeof(float));
+}
+
+// ritz_rotate: Out[:, :b2] = V[:, voff : +m] C, res2[j] = || B[:, boff : +m] C[:, j] - theta[j] Out[:, j] ||^2
+extern "C" int gemhip_test_hope_ritz(int64_t n, const float *V_host, int32_t ldv, int32_t voff, const float *B_host, int32_t ldb, int32_t boff, int32_t m,
+                                     const double *C_host, const double *theta_host, int32_t b2, float *Out_inout, int32_t ldo, double *res2_out)
+{
+    GEMHIP_REQUIRE(n >= 1 && m >= 1 && b2 >= 1 && V_host && B_host && C_host && theta_host && Out_inout && res2_out, "test_hope_ritz: bad arguments");
+    GEMHIP_REQUIRE(voff >= 0 && boff >= 0 && voff + m <= ldv && boff + m <= ldb && ldo >= b2, "test_hope_ritz: bad shapes");
+    Hope H; H.n = n;
+    DevBuf<float> dV, dB, dO;
+    HOPE_TRY(H, dV.upload(V_host, (size_t)n * ldv)); HOPE_TRY(H, dB.upload(B_host, (size_t)n * ldb)); HOPE_TRY(H, dO.upload(Out_inout, (size_t)n * ldo));
+    const std::vector<double> C(C_host, C_host + (size_t)m * b2), theta(theta_host, theta_host + b2);
+    std::vector<double> res2;
+    ritz_rotate(H, dV + voff, ldv, dB + boff, ldb, m, C, theta, b2, dO, ldo, res2);
+    if (!H.err) std::copy(res2.begin(), res2.end(), res2_out);
+    return hook_download(H, Out_inout, dO, (size_t)n * ldo * sizeof(float));
+}
+
+// colmax: val[j] = the entry of X[:, j] (j < mc) with the largest magnitude, first row on ties.  variant: 0 = production choice, 1 = one pass
+// (hope_colmax_kernel), 2 = two passes (hope_colmax1/2_kernel).
+extern "C" int gemhip_test_hope_colmax(int64_t n, const float *X_host, int32_t ld, int32_t mc, int32_t variant, float *val_out)
+{
+    GEMHIP_REQUIRE(n >= 1 && X_host && val_out && mc >= 1 && ld >= mc && variant >= 0 && variant <= 2, "test_hope_colmax: bad arguments");
+    Hope H; H.n = n;
+    if (variant) H.force_colmax2 = variant - 1;
+    DevBuf<float> dX, dv;
+    HOPE_TRY(H, dX.upload(X_host, (size_t)n * ld));
+    HOPE_TRY(H, dv.reserve(mc));
+    colmax(H, dX, ld, mc, dv);
+    return hook_download(H, val_out, dv, (size_t)mc * sizeof(float));
+}
+
+// project_out: W[:, :cols] -= V[:, :m] (V[:, :m]^T W[:, :cols]).  woff < 0: W_inout is its own n x ldw block.  woff >= 0: as in the solvers, W is the
+// column block [woff, woff + cols) of V's own block (W = V + woff, ldw = ldv) and W_inout (n x ldv) receives that whole block back.
+extern "C" int gemhip_test_hope_project_out(int64_t n, const float *V_host, int32_t ldv, int32_t m, float *W_inout, int32_t ldw, int32_t cols, int32_t woff)
+{
+    GEMHIP_REQUIRE(n >= 1 && V_host && W_inout && m >= 1 && cols >= 1 && m <= ldv && cols <= ldw, "test_hope_project_out: bad arguments");
+    GEMHIP_REQUIRE(woff < 0 || (woff >= m && woff + cols <= ldv && ldw == ldv), "test_hope_project_out: bad shared block");
+    Hope H; H.n = n;
+    DevBuf<float> dV, dW;
+    HOPE_TRY(H, dV.upload(V_host, (size_t)n * ldv));
+    if (woff < 0) HOPE_TRY(H, dW.upload(W_inout, (size_t)n * ldw));
+    project_out(H, dV, ldv, m, woff < 0 ? dW.get() : dV.get() + woff, ldw, cols);
+    return hook_download(H, W_inout, woff < 0 ? dW.get() : dV.get(), (size_t)n * ldw * sizeof(float));
+}
+
+// apply_sym_op: Out[:, :cols] = alpha Op X + wa W + wb W2; kind 0: Op = the CSR matrix, kind 2: Op = (I - A)^T (I - A) (A as given: the caller
+// normalises the rows).  The n x cols scratch of kind 2 is the hook's own.
+extern "C" int gemhip_test_hope_sym_op(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t kind, float alpha,
+                                       const float *X_host, int32_t ldx, int32_t cols, float wa, const float *W_host, int32_t ldw, float wb,
+                                       const float *W2_host, int32_t ldw2, float *Out_inout, int32_t ldo)
+{
+    GEMHIP_REQUIRE(hook_csr_ok(n, nnz, row_ptr, col), "test_hope_sym_op: bad CSR arguments");
+    GEMHIP_REQUIRE((kind == 0 || kind == 2) && X_host && Out_inout && cols >= 1 && cols <= 512 && ldx >= cols && ldo >= cols, "test_hope_sym_op: bad arguments");
+    GEMHIP_REQUIRE((!W_host || ldw >= cols) && (!W2_host || ldw2 >= cols), "test_hope_sym_op: bad addend arguments");
+    Hope H;
+    hook_upload_csr(H, n, nnz, row_ptr, col, w, true);
+    H.mode = kind;
+    DevBuf<float> dX, dW, dW2, dT, dO;
+    HOPE_TRY(H, dX.upload(X_host, (size_t)n * ldx));
+    if (W_host) HOPE_TRY(H, dW.upload(W_host, (size_t)n * ldw));
+    if (W2_host) HOPE_TRY(H, dW2.upload(W2_host, (size_t)n * ldw2));
+    HOPE_TRY(H, dT.reserve((size_t)n * cols));
+    HOPE_TRY(H, dO.upload(Out_inout, (size_t)n * ldo));
+    apply_sym_op(H, kind, alpha, dX, ldx, cols, dT, cols, dO, ldo, wa, dW, ldw, wb, dW2, ldw2);
+    return hook_download(H, Out_inout, dO, (size_t)n * ldo * sizeof(float));
+}
+
+// lincomb: Out[:, :b] = a X + b2 Y + c Z.  out_is_x: Out is the device block of X (Out_inout's contents are X, ldx = ldo; X_host NULL).
+extern "C" int gemhip_test_hope_lincomb(int64_t n, int32_t b, float a, const float *X_host, int32_t ldx, float b2, const float *Y_host, int32_t ldy, float c,
+                                        const float *Z_host, int32_t ldz, int32_t out_is_x, float *Out_inout, int32_t ldo)
+{
+    GEMHIP_REQUIRE(n >= 1 && b >= 1 && Y_host && Z_host && Out_inout && ldy >= b && ldz >= b && ldo >= b, "test_hope_lincomb: bad arguments");
+    GEMHIP_REQUIRE(out_is_x ? X_host == nullptr : (X_host != nullptr && ldx >= b), "test_hope_lincomb: X_host and out_is_x exclude each other");
+    Hope H; H.n = n;
+    DevBuf<float> dX, dY, dZ, dO;
+    if (X_host) HOPE_TRY(H, dX.upload(X_host, (size_t)n * ldx));
+    HOPE_TRY(H, dY.upload(Y_host, (size_t)n * ldy)); HOPE_TRY(H, dZ.upload(Z_host, (size_t)n * ldz));
+    HOPE_TRY(H, dO.upload(Out_inout, (size_t)n * ldo));
+    lincomb(H, b, a, out_is_x ? dO.get() : dX.get(), out_is_x ? ldo : ldx, b2, dY, ldy, c, dZ, ldz, dO, ldo);
+    return hook_download(H, Out_inout, dO, (size_t)n * ldo * sizeof(float));
+}
+
+// randn: X[:, :b] = the solvers' starting block for `seed`
+extern "C" int gemhip_test_hope_randn(int64_t n, int32_t b, int32_t ld, uint64_t seed, float *X_inout)
+{
+    GEMHIP_REQUIRE(n >= 1 && b >= 1 && ld >= b && X_inout, "test_hope_randn: bad arguments");
+    Hope H; H.n = n;
+    DevBuf<float> dX;
+    HOPE_TRY(H, dX.upload(X_inout, (size_t)n * ld));
+    randn(H, dX, b, ld, seed);
+    return hook_download(H, X_inout, dX, (size_t)n * ld * sizeof(float));
 }

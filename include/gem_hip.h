@@ -425,7 +425,10 @@ int gemhip_lle(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *co
  *   sym_eig : host fp64 symmetric eigensolver used for the projected problems (A overwritten by
  *             eigenvectors in columns, w ascending) -- pure host code, callable without a GPU;
  *   spmm    : Y[n][b] = alpha * A X (+ Wadd)        gram : G[m1][m2] = X^T Y  (fp64 out, MFMA fp32)
- *   tsgemm  : Out[n][b2] = (Src or 0) + alpha * X[n][m] C[m][b2]   (C given in fp64, MFMA fp32). */
+ *   tsgemm  : Out[n][b2] = (Src or 0) + alpha * X[n][m] C[m][b2]   (C given in fp64, MFMA fp32).
+ * These three pass compact blocks, the plain epilogue and distinct buffers only; the gemhip_test_hope_* hooks below reach the
+ * same host functions with the solvers' leading dimensions, column offsets, three-term epilogue and aliased blocks, and the
+ * blocks that have no export here (Ritz rotation, column arg-max, device projection, the LLE operator, lincomb, randn). */
 int gemhip_sym_eig(int32_t n, double *A_inout, double *w_out);
 int gemhip_sym_eig_builtin(int32_t n, double *A_inout, double *w_out);
 /* The m largest eigenpairs only (what the Rayleigh-Ritz step consumes): Householder reduction, QL eigenvalues, inverse
@@ -448,6 +451,60 @@ int gemhip_hope_gram(int64_t n, int32_t m1, int32_t m2, const float *X_host, con
                      double *G_host);
 int gemhip_hope_tsgemm(int64_t n, int32_t m, int32_t b2, const float *X_host, const double *C_host,
                        float alpha, const float *Src_host, float *Out_host);
+
+/* -------------------------------------------------- test hooks (HOPE building blocks under the solvers' calling conventions)
+ * Like gemhip_test_wave_sum6: not part of the product API.  Each hook uploads its host blocks, calls the host function the
+ * solvers call (spmm, gram, gram2, tsgemm, ritz_rotate, colmax, project_out, apply_sym_op, lincomb, randn in
+ * gem_amd/csrc/hope.hip) on a state of its own, and copies the result back; blocking.  Unlike the three exports above,
+ * every dense block has its own leading dimension (ld >= logical columns; an "off" argument is a column offset into the
+ * block, as in `Vall + nl`), and blocks named *_inout are uploaded WHOLE before the call and downloaded WHOLE after it:
+ * a caller that fills the padding columns with a sentinel sees every write outside the logical columns.
+ *   spmm       : Y[:, :b] = alpha A X + wa W + wb W2.  variant 0 = production dispatch, 1 = one row per wavefront
+ *                (hope_spmm_kernel), 2 / 4 / 8 = hope_spmm16_kernel with that many gathers in flight (b <= 128; widths whose
+ *                instantiation list lacks that U get the nearest smaller one, as GEMHIP_HOPE_SPMM16_U does).  w_is_x: W is
+ *                the very device block of X (the (I + M) X and X - P X calls); w2_is_y: W2 is the very device block of Y,
+ *                holding Y_inout's contents (apply_sym_op kind 2).  launched_out (may be NULL) receives the instantiation the
+ *                dispatch chose: {CPL16, U} of hope_spmm16_kernel or {CPL, 0} of hope_spmm_kernel.  Without an override the environment variables
+ *                GEMHIP_HOPE_SPMM16 / GEMHIP_HOPE_SPMM16_U / GEMHIP_HOPE_COLMAX2 decide, as in the solvers.
+ *   gram       : G[m1][m2] = X[:, xoff:+m1]^T Y[:, yoff:+m2] (fp64); Y_host NULL = Y is X's device block; Gf_host (optional):
+ *                the same values rounded to fp32 on the device (what project_out feeds its GEMM).
+ *   gram2      : two such products in one call (shared scratch, one round trip).
+ *   tsgemm     : Out[:, :b2] = (Src or 0) + alpha X[:, xoff:+m] C; in_place: Src is Out's device block (Out_inout's contents).
+ *   ritz       : Out[:, :b2] = V[:, voff:+m] C;  res2[j] = || B[:, boff:+m] C[:, j] - theta[j] Out[:, j] ||^2  (C: m x b2, fp64).
+ *   colmax     : val[j] = the entry of column j < mc with the largest magnitude, the first row on ties.  variant 0 = production
+ *                choice, 1 = one pass (hope_colmax_kernel), 2 = two passes (hope_colmax1/2_kernel).
+ *   project_out: W[:, :cols] -= V[:, :m] (V[:, :m]^T W[:, :cols]) without a host round trip.  woff < 0: W is a block of its own;
+ *                woff >= 0: W = columns [woff, woff + cols) of V's block (ldw = ldv), and W_inout receives that whole block.
+ *   sym_op     : Out[:, :cols] = alpha Op X + wa W + wb W2; kind 0: Op = A (CSR); kind 2: Op = (I - A)^T (I - A), A^T built
+ *                as gemhip_lle builds it (rows are NOT normalised here).  W_host / W2_host may be NULL.
+ *   lincomb    : Out[:, :b] = a X + b2 Y + c Z; out_is_x: X is Out's device block (X_host NULL, Out_inout holds X).
+ *   randn      : X[:, :b] = the solvers' Gaussian starting block for `seed`. */
+int gemhip_test_hope_spmm(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t variant,
+                          float alpha, int32_t b, const float *X_host, int32_t ldx, float wa, const float *W_host, int32_t ldw,
+                          float wb, const float *W2_host, int32_t ldw2, int32_t w_is_x, int32_t w2_is_y, float *Y_inout,
+                          int32_t ldy, int32_t *launched_out);
+int gemhip_test_hope_gram(int64_t n, const float *X_host, int32_t ldx, int32_t xoff, int32_t m1, const float *Y_host,
+                          int32_t ldy, int32_t yoff, int32_t m2, double *G_host, float *Gf_host);
+int gemhip_test_hope_gram2(int64_t n, const float *Xa_host, int32_t ldxa, int32_t xaoff, int32_t ma1, const float *Ya_host,
+                           int32_t ldya, int32_t yaoff, int32_t ma2, double *Ga_host, const float *Xb_host, int32_t ldxb,
+                           int32_t xboff, int32_t mb1, const float *Yb_host, int32_t ldyb, int32_t yboff, int32_t mb2,
+                           double *Gb_host);
+int gemhip_test_hope_tsgemm(int64_t n, const float *X_host, int32_t ldx, int32_t xoff, int32_t m, const double *C_host,
+                            int32_t b2, float alpha, const float *Src_host, int32_t lds, int32_t in_place, float *Out_inout,
+                            int32_t ldo);
+int gemhip_test_hope_ritz(int64_t n, const float *V_host, int32_t ldv, int32_t voff, const float *B_host, int32_t ldb,
+                          int32_t boff, int32_t m, const double *C_host, const double *theta_host, int32_t b2,
+                          float *Out_inout, int32_t ldo, double *res2_out);
+int gemhip_test_hope_colmax(int64_t n, const float *X_host, int32_t ld, int32_t mc, int32_t variant, float *val_out);
+int gemhip_test_hope_project_out(int64_t n, const float *V_host, int32_t ldv, int32_t m, float *W_inout, int32_t ldw,
+                                 int32_t cols, int32_t woff);
+int gemhip_test_hope_sym_op(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t kind,
+                            float alpha, const float *X_host, int32_t ldx, int32_t cols, float wa, const float *W_host,
+                            int32_t ldw, float wb, const float *W2_host, int32_t ldw2, float *Out_inout, int32_t ldo);
+int gemhip_test_hope_lincomb(int64_t n, int32_t b, float a, const float *X_host, int32_t ldx, float b2, const float *Y_host,
+                             int32_t ldy, float c, const float *Z_host, int32_t ldz, int32_t out_is_x, float *Out_inout,
+                             int32_t ldo);
+int gemhip_test_hope_randn(int64_t n, int32_t b, int32_t ld, uint64_t seed, float *X_inout);
 
 /* -------------------------------------------------- evaluation
  * Average precision of graph reconstruction for SAMPLED nodes, with the exact semantics of

@@ -21,12 +21,18 @@ _lib = None
 def build(force=False):
     """make -C oracle : compiles liboracle.so and (only where /root/reference exists)
     the real reference binaries into oracle/_ref/."""
+    import fcntl
     srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith('.c')]
-    stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
-    if stale:
-        subprocess.check_call(['make', '-s', '-C', _HERE, '_build/liboracle.so'])
-    if os.path.exists('/root/reference/gem/c_src/gf.cpp') and not (os.path.exists(REF_GF) and os.path.exists(REF_N2V) and os.path.exists(REF_FAKETIME)):
-        subprocess.check_call(['make', '-s', '-C', _HERE, 'ref'])
+    os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
+    # One builder at a time: the ranks a test spawns (tests/test_multi_gpu_cpu.py) all come here at once when the library is missing or stale,
+    # and two makes of one target trip over each other.  The staleness test is made under the lock, so the second process finds the first one's file.
+    with open(os.path.join(os.path.dirname(LIB_PATH), '.build.lock'), 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+        if stale:
+            subprocess.check_call(['make', '-s', '-C', _HERE, '_build/liboracle.so'])
+        if os.path.exists('/root/reference/gem/c_src/gf.cpp') and not (os.path.exists(REF_GF) and os.path.exists(REF_N2V) and os.path.exists(REF_FAKETIME)):
+            subprocess.check_call(['make', '-s', '-C', _HERE, 'ref'])
     return LIB_PATH
 
 
