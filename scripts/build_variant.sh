@@ -12,6 +12,6 @@ for f in n2v sgns_hogwild sgns_det sgns_part; do
 done
 wait
 python -m gem_amd.build > /dev/null
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o gem_amd/libgem_hip_$suf.so gem_amd/build/eval.hip.o gem_amd/build/gf.hip.o gem_amd/build/hope.hip.o gem_amd/build/runtime.hip.o \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o gem_amd/libgem_hip_$suf.so gem_amd/build/eval.hip.o gem_amd/build/gf.hip.o gem_amd/build/hope.hip.o gem_amd/build/sym_eig.hip.o gem_amd/build/runtime.hip.o \
     gem_amd/build/multi.hip.o gem_amd/build/$suf/n2v.hip.o gem_amd/build/$suf/sgns_hogwild.hip.o gem_amd/build/$suf/sgns_det.hip.o gem_amd/build/$suf/sgns_part.hip.o -ldl
 echo gem_amd/libgem_hip_$suf.so

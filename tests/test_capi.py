@@ -221,3 +221,26 @@ def test_gf_plan_rejects_edge_orders_the_reference_loop_cannot_be_scheduled_for(
     rc = L.gemhip_gf_plan_create(4, 3, _hip.ptr(src, C.c_int32), _hip.ptr(dst, C.c_int32), None, 8, 0, 4, C.byref(plan))
     assert rc == -1 and not plan.value
     assert b'partly updated' in L.gemhip_last_error()
+
+
+def test_operator_entry_points_reject_a_bad_csr_before_any_device_call():
+    """gemhip_hope_plan_create, gemhip_lap_eigmap and gemhip_lle share one CSR validator (hope.hip check_csr).  A 3-node path graph whose
+    row_ptr[n] != nnz, and the same graph with one column index equal to n: GEMHIP_E_INVALID and these exact messages (recorded from the library
+    before the validator was shared).  Validation only -- the calls return before their first HIP call, so this runs without a GPU."""
+    import ctypes as C
+    import numpy as np
+    L = _hip.lib()
+    n, nnz = 3, 4
+    path_rp = np.array([0, 1, 3, 4], np.int64); path_col = np.array([1, 0, 2, 1], np.int32)
+    cases = ((np.array([0, 1, 3, 3], np.int64), path_col, b'%s: row_ptr inconsistent with nnz'),
+             (path_rp, np.array([1, 0, 3, 1], np.int32), b'%s: column 3 outside [0,3)'))
+    V = np.zeros((n, 1), np.float32); s = np.zeros(1, np.float32)
+    for rp, col, msg in cases:
+        plan = C.c_void_p()
+        rc = L.gemhip_hope_plan_create(n, nnz, _hip.ptr(rp, C.c_int64), _hip.ptr(col, C.c_int32), None, 0.1, C.byref(plan))
+        assert rc == _hip.E_INVALID and not plan.value
+        assert L.gemhip_last_error() == msg % b'hope'
+        for fn, who in ((L.gemhip_lap_eigmap, b'lap_eigmap'), (L.gemhip_lle, b'lle')):
+            rc = fn(n, nnz, _hip.ptr(rp, C.c_int64), _hip.ptr(col, C.c_int32), None, 1, 0, 2, 1, 1e-6, 1, _hip.ptr(V, C.c_float), _hip.ptr(s, C.c_float), None)
+            assert rc == _hip.E_INVALID
+            assert L.gemhip_last_error() == msg % who
