@@ -8,10 +8,12 @@
 //        2nd-order bias by rejection sampling inside the walk, no sum(deg^2) tables)
 //   SimulateWalk/AliasDrawInt             -> n2v_walk_kernel   (one lane = one walker)
 //   LearnVocab                            -> n2v_vocab_kernel
-//   InitUnigramTable                      -> host Vose in fp64 (O(n), once)
+//   InitUnigramTable                      -> host Vose in fp64 (O(n), once): sgns_plan.hip build_unigram_tables
 //   InitPosEmb/InitNegEmb                 -> sgns_init_kernel
 //   TrainModel (Hogwild over walks)       -> sgns_win_kernel / sgns_kernel (sgns.hpp; one wavefront = one walk), instantiated in
-//        sgns_hogwild.hip, sgns_det.hip and sgns_part.hip (one bucket of the partitioned N-GPU schedule); this file holds the C ABI and the launch rule
+//        sgns_hogwild.hip, sgns_det.hip and sgns_part.hip (one bucket of the partitioned N-GPU schedule)
+// This file holds the kernels of everything but TrainModel and the C ABI: it validates, moves data, and launches.  What a launch looks like and what
+// the unigram tables contain is host arithmetic without a device: sgns_plan.hip (VocabStats, SgnsKnobs, plan_sgns_launch, bucket_knobs, UnigramTables).
 //
 // All randomness is a counter-based Philox4x32-10 stream keyed by (seed, walk, position,
 // purpose): results do not depend on scheduling, and the CPU oracle reproduces walks,
@@ -43,93 +45,6 @@ __host__ __device__ __forceinline__ uint32_t perm_node(uint32_t j, uint32_t n, u
     return j;
 }
 }  // namespace
-
-// How concentrated the row traffic of TrainModel is: what the Hogwild launch rule (plan_sgns_launch) needs to know about the vocabulary.
-struct VocabStats {
-    double n = 0.0, total = 0.0, max = 0.0, active = 0.0;     // table rows, tokens, largest count, nodes that occur at all
-    double z = 0.0;                    // sum of count^0.75
-    double n_eff = 0.0;                // 1 / sum_v q_v^2, q = unigram^0.75 distribution: the table size a uniform graph with the same collision rate would have
-    double touch2 = 0.0;               // sum_v (p_v + 5 q_v)^2, p = token share: collision rate of the rows a (centre, context) pair TOUCHES (its context row + five negatives)
-    mutable std::vector<int32_t> cnt_desc;     // token counts, descending (after sort_once), and ...
-    mutable std::vector<double> u2_prefix;     // ... u2_prefix[i] = sum of (count^0.75)^2 over the i largest counts
-    mutable std::vector<double> c_prefix, u_prefix;   // ... sums of count and of count^0.75 over the i largest counts
-    void build(const int32_t *cnt, int64_t len)
-    {
-        double tot = 0.0, mx = 0.0, zz = 0.0, z2 = 0.0, c2 = 0.0, cu = 0.0;
-        n = (double)len; active = 0.0;
-        for (int64_t i = 0; i < len; ++i) {
-            const int32_t c = cnt[i];
-            if (c <= 0) continue;
-            tot += c; mx = std::max(mx, (double)c); active += 1.0;
-            const double u = std::pow((double)c, 0.75);
-            zz += u; z2 += u * u; c2 += (double)c * c; cu += (double)c * u;
-        }
-        total = tot; max = mx; z = zz;
-        n_eff = z2 > 0.0 ? zz * zz / z2 : n;
-        touch2 = (tot > 0.0 && zz > 0.0) ? c2 / (tot * tot) + 10.0 * cu / (tot * zz) + 25.0 * z2 / (zz * zz) : 0.0;
-        cnt_desc.assign(cnt, cnt + len);                     // sorted (and the prefix sums formed) only if the rule has to look at the cold rows
-        u2_prefix.clear();
-    }
-    void sort_once() const
-    {
-        if (!u2_prefix.empty()) return;
-        std::sort(cnt_desc.begin(), cnt_desc.end(), std::greater<int32_t>());
-        u2_prefix.assign(cnt_desc.size() + 1, 0.0);
-        c_prefix.assign(cnt_desc.size() + 1, 0.0); u_prefix.assign(cnt_desc.size() + 1, 0.0);
-        for (size_t i = 0; i < cnt_desc.size(); ++i) {
-            const double u = cnt_desc[i] > 0 ? std::pow((double)cnt_desc[i], 0.75) : 0.0;
-            u2_prefix[i + 1] = u2_prefix[i] + u * u;
-            c_prefix[i + 1] = c_prefix[i] + (cnt_desc[i] > 0 ? (double)cnt_desc[i] : 0.0);
-            u_prefix[i + 1] = u_prefix[i] + u;
-        }
-    }
-    // hot row-operations per trained (centre, context) pair when the rows with count >= thr are hot: P(the context is hot) + 5 x P(a negative is hot)
-    double hot_ops_per_pair(double thr) const
-    {
-        if (cnt_desc.empty() || z <= 0.0 || total <= 0.0) return 0.0;
-        sort_once();
-        const size_t nhot = (size_t)(std::lower_bound(cnt_desc.begin(), cnt_desc.end(), thr, [](int32_t c, double t) { return (double)c >= t; }) - cnt_desc.begin());
-        return c_prefix[nhot] / total + 5.0 * u_prefix[nhot] / z;
-    }
-    // effective table size of the negative-sampling distribution over the rows that are NOT hot (count < thr): hot rows take atomic adds and lose nothing
-    double n_eff_cold(double thr) const
-    {
-        if (cnt_desc.empty() || z <= 0.0) return n;
-        sort_once();
-        const size_t nhot = (size_t)(std::lower_bound(cnt_desc.begin(), cnt_desc.end(), thr, [](int32_t c, double t) { return (double)c >= t; }) - cnt_desc.begin());
-        const double s2 = (u2_prefix.back() - u2_prefix[nhot]) / (z * z);
-        return s2 > 0.0 ? 1.0 / s2 : 1e300;
-    }
-};
-
-// The knobs of a handle that steer the SGNS launch (gemhip_n2v_set_max_waves, gemhip_sgns_set_window_cache / _hogwild / _hot_rows) ...
-struct SgnsKnobs {
-    int32_t max_waves = 0;            // 0 = auto (plan_sgns_launch)
-    int32_t cache_radius = -1;        // sgns_win_kernel LDS window radius: -1 auto, 0 = off (sgns_kernel)
-    int32_t cache_delta = -1;         // -1 auto, 0 overwrite on leave, 1 delta write-back
-    int32_t prefetch = 2;             // pairs whose negative rows are requested ahead: 2 (default) or 1 (d == 64/128/256.., whole window cached)
-    int32_t reload = 1;               // Hogwild launches: update negative rows as they are at store time (second fetch) and the centre row by atomic add
-    int32_t hot_count = -1;           // nodes with at least this many tokens never enter the LDS window: -1 auto (tokens / ((W-1) x (2R+1))), 0 off
-    int32_t window_span = 0;          // positions of a walk whose context rows a wavefront holds at once: 0 = 2R+1 (the sliding window); the whole walk in the bucket kernel's whole-walk mode
-    bool part = false;                // a bucket launch of the partitioned schedule (sgns_win_kernel<PART>: as-loaded window copies in global scratch, 3 wavefronts per SIMD)
-    double duty = 1.0;                // fraction of a wavefront's time spent in pair steps (negative rows open); < 1 only for the buckets of the partitioned schedule
-    double touch_scale = 1.0;         // factor on VocabStats::touch2 (bucket launches: the pairs of ONE bucket touch the rows of two partitions only: parts x duty)
-    bool has_local_hot = false;       // this corpus HAS locally hot nodes (ensure_hotkey): the launch carries the staging row and a hot threshold even without count-hot rows
-    int32_t local_hot = 8;            // LOCALLY HOT ROWS: a node with at least this many tokens per walk that contains it is treated as a hot row (0: off)
-    int32_t neg_count = 0;            // fresh bit 2: token count from which a negative row is updated by atomic add (0: every row)
-    int32_t fresh = 0;                // FRESH HOT ROWS (sgns.hpp, SgnsArgs::fresh): bit 0 hot centre words by returning atomics, bit 1 hot negatives re-read before the dot products
-    bool node_id_layout = false;      // the unigram table the launch draws from is in node-id order (gemhip_n2v_build_unigram), not the binary's: half the concurrent-touch bound (plan_sgns_launch)
-};
-// ... and what a launch of TrainModel over `nwalks` walks then looks like (pure host arithmetic: gemhip_sgns_plan_launch exposes it to the CPU tests)
-struct SgnsLaunchPlan {
-    bool window = false;              // sgns_win_kernel (LDS window) or sgns_kernel
-    bool delta = false;               // window kernel: delta write-back (the Hogwild instantiation)
-    int R = 0;                        // window radius
-    int64_t waves = 1;                // concurrent wavefronts = concurrent walks
-    int32_t hot_thr = 0;              // token count from which a row is "hot" (0: none)
-    size_t lds = 0;                   // dynamic LDS bytes per workgroup
-    int blocks = 1, threads = 64;
-};
 
 struct gemhip_n2v {
     int64_t n = 0, nnz = 0;
@@ -170,7 +85,7 @@ struct gemhip_n2v {
     float *SynPos = nullptr, *SynNeg = nullptr;   // what the kernels train: syn_own's blocks, or the caller's tables (gemhip_sgns_init)
     DevBuf<float> syn_own[2];         // empty while the tables are borrowed
     SgnsKnobs kn;                     // launch knobs (setters below; environment overrides read once in gemhip_n2v_create)
-    DevBuf<int32_t> d_hotkey, d_wcount; DevBuf<unsigned int> d_nlocal; int hotkey_state = 0; int64_t n_local_hot = 0;   // LOCALLY HOT ROWS (ensure_hotkey)
+    DevBuf<int32_t> d_hotkey, d_wcount; DevBuf<unsigned int> d_nlocal; int hotkey_state = 0; int64_t n_local_hot = 0;   // LOCALLY HOT ROWS (build_hotkey)
     SgnsLaunchPlan last_plan;         // what the last gemhip_sgns_train / _train_part on this handle actually launched (gemhip_sgns_last_launch)
     int32_t last_fresh = 0;
     VocabStats vs;                    // vocabulary statistics (gemhip_n2v_build_unigram*): how concentrated the row traffic is -> plan_sgns_launch
@@ -721,61 +636,68 @@ extern "C" int gemhip_n2v_counts_ptr(gemhip_n2v_t h, void **d_counts)
     return GEMHIP_OK;
 }
 
-
-// InitUnigramTable (ELF @0x40e520) on a count vector: count^0.75, Vose in fp64, stacks popped from the back.
-static bool vose_unigram(const int32_t *cnt, int64_t n, int64_t stride, std::vector<float> &Uf, std::vector<int32_t> &K)
+// ------------------------------------------------------------------ unigram tables
+// The four builders below validate, obtain the token counts (and, for the binary's layout, the first-appearance order), call the one host builder
+// (sgns_plan.hip build_unigram_tables: Vose per partition, both layouts), upload through the one path of their table set and copy their optional
+// outputs in the index space gem_hip.h documents for each.  The handle changes only when a build succeeds.
+static int read_counts(gemhip_n2v_t h, std::vector<int32_t> &cnt)
 {
-    std::vector<double> U(n);
-    std::vector<int32_t> small, large;
-    K.assign(n, 0);
-    double total = 0.0;
-    for (int64_t i = 0; i < n; ++i) { U[i] = std::pow((double)cnt[i * stride], 0.75); total += U[i]; }
-    if (!(total > 0.0)) return false;
-    for (int64_t i = 0; i < n; ++i) U[i] /= total;
-    small.reserve(n); large.reserve(n);
-    for (int64_t i = 0; i < n; ++i) {
-        U[i] = U[i] * (double)n;
-        if (U[i] < 1.0) small.push_back((int32_t)i); else large.push_back((int32_t)i);
-    }
-    while (!small.empty() && !large.empty()) {
-        const int32_t s = small.back(); small.pop_back();
-        const int32_t l = large.back(); large.pop_back();
-        K[s] = l;
-        U[l] = U[l] + U[s] - 1.0;
-        if (U[l] < 1.0) small.push_back(l); else large.push_back(l);
-    }
-    for (int32_t s : small) U[s] = 1.0;
-    for (int32_t l : large) U[l] = 1.0;
-    Uf.resize(n);
-    for (int64_t i = 0; i < n; ++i) Uf[i] = (float)U[i];
-    return true;
+    GEMHIP_CHECK(hipDeviceSynchronize());
+    cnt.resize(h->n);
+    PhaseScope ph(PH_D2H);
+    GEMHIP_CHECK(hipMemcpy(cnt.data(), h->d_counts, h->n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return GEMHIP_OK;
+}
+
+static int host_tables(const std::vector<int32_t> &cnt, const int32_t *order, int32_t parts, int32_t flags, UnigramTables &T)
+{
+    PhaseScope ph(PH_HOST);
+    return build_unigram_tables(cnt.data(), (int64_t)cnt.size(), order, parts, flags, T);
+}
+
+// {bits of U[i], K[i]} interleaved: one 8-byte gather instead of two 4-byte gathers
+static std::vector<uint2> interleave_uk(const std::vector<float> &U, const std::vector<int32_t> &K)
+{
+    std::vector<uint2> UK(U.size());
+    for (size_t i = 0; i < U.size(); ++i) { uint32_t ub; memcpy(&ub, &U[i], 4); UK[i] = make_uint2(ub, (uint32_t)K[i]); }
+    return UK;
+}
+
+// One table set of the handle -- d_UT / d_KT / d_UK / d_KTslot, or the per-partition d_UTp / d_KTp / d_UKp / d_KTslotp: the alias arrays by local row
+// (alias_arrays; the single table in the binary's layout is read through UK and the slot table only), their interleave, and the slot table where the
+// layout has one (entries beyond a partition's slot count go up as 0; never read: a launch draws slots below that count)
+static int upload_unigram(const UnigramTables &T, bool alias_arrays, DevBuf<float> &UT, DevBuf<int32_t> &KT, DevBuf<uint2> &UK, DevBuf<int32_t> &KTslot)
+{
+    PhaseScope ph(PH_H2D);
+    const size_t n = T.U.size();
+    const std::vector<uint2> uk = interleave_uk(T.U, T.K);
+    std::vector<int32_t> Sdev(T.slot);
+    for (auto &v : Sdev) if (v < 0) v = 0;
+    if (alias_arrays) { GEMHIP_CHECK(UT.upload(T.U.data(), n)); GEMHIP_CHECK(KT.upload(T.K.data(), n)); }
+    GEMHIP_CHECK(UK.upload(uk.data(), n));
+    if (!Sdev.empty()) GEMHIP_CHECK(KTslot.upload(Sdev.data(), n));
+    return GEMHIP_OK;
+}
+
+// ... and what a successful per-partition build leaves on the handle
+static void commit_parts(gemhip_n2v_t h, UnigramTables &T, int32_t parts, bool vocab_order)
+{
+    h->vs = std::move(T.vs); h->vs_part = std::move(T.vs_part); h->part_off = std::move(T.part_off); h->part_slots = std::move(T.part_slots);
+    h->parts = parts; h->skp_state = -1; h->parts_vocab_order = vocab_order;
 }
 
 extern "C" int gemhip_n2v_build_unigram(gemhip_n2v_t h, int32_t *counts_out, float *UT_out, int32_t *KT_out)
 {
     GEMHIP_REQUIRE(h, "n2v_build_unigram: NULL handle");
-    GEMHIP_CHECK(hipDeviceSynchronize());
-    const int64_t n = h->n;
-    std::vector<int32_t> cnt(n), K;
-    std::vector<float> Uf;
-    { PhaseScope ph(PH_D2H); GEMHIP_CHECK(hipMemcpy(cnt.data(), h->d_counts, n * sizeof(int32_t), hipMemcpyDeviceToHost)); }
-    {
-        PhaseScope ph(PH_HOST);
-        GEMHIP_REQUIRE(vose_unigram(cnt.data(), n, 1, Uf, K), "n2v_build_unigram: empty vocabulary (no walks?)");
-        h->vs.build(cnt.data(), (int64_t)cnt.size());
-    }
-    PhaseScope ph_up(PH_H2D);
-    GEMHIP_CHECK(h->d_UT.upload(Uf.data(), n));
-    GEMHIP_CHECK(h->d_KT.upload(K.data(), n));
-    {
-        std::vector<uint2> UK((size_t)n);
-        for (int64_t i = 0; i < n; ++i) { uint32_t ub; memcpy(&ub, &Uf[i], 4); UK[i] = make_uint2(ub, (uint32_t)K[i]); }
-        GEMHIP_CHECK(h->d_UK.upload(UK.data(), n));
-    }
+    std::vector<int32_t> cnt; UnigramTables T;
+    if (int rc = read_counts(h, cnt)) return rc;
+    GEMHIP_REQUIRE(host_tables(cnt, nullptr, 1, 0, T) < 0, "n2v_build_unigram: empty vocabulary (no walks?)");
+    if (int rc = upload_unigram(T, true, h->d_UT, h->d_KT, h->d_UK, h->d_KTslot)) return rc;
+    h->vs = std::move(T.vs);
     h->unigram_ready = true; h->vocab_order = false; h->sk_state = -1; h->hotkey_state = 0;
     if (counts_out) std::copy(cnt.begin(), cnt.end(), counts_out);
-    if (UT_out) std::copy(Uf.begin(), Uf.end(), UT_out);
-    if (KT_out) std::copy(K.begin(), K.end(), KT_out);
+    if (UT_out) std::copy(T.U.begin(), T.U.end(), UT_out);
+    if (KT_out) std::copy(T.K.begin(), T.K.end(), KT_out);
     return GEMHIP_OK;
 }
 
@@ -821,35 +743,22 @@ static int first_appearance_order(gemhip_n2v_t h, const int32_t *d_tokens, int64
 extern "C" int gemhip_n2v_build_unigram_vocab_order(gemhip_n2v_t h, int32_t flags, int64_t *n_vocab_out, int32_t *order_out, float *UT_out, int32_t *KT_out)
 {
     GEMHIP_REQUIRE(h && h->d_walks && h->nwalks > 0, "n2v_build_unigram_vocab_order: no walks");
-    const int64_t n = h->n;
-    std::vector<int32_t> back, cnt;              // back: renamed id -> node
+    std::vector<int32_t> back, cnt; UnigramTables T;             // back: renamed id -> node
     if (int rc = first_appearance_order(h, h->d_walks, h->nwalks * h->walk_len, back, cnt)) return rc;
-    PhaseScope ph_host(PH_HOST);
-    int64_t N = 0;
-    while (N < n && cnt[back[N]] > 0) ++N;             // the nodes that occur come first (a node occurs iff it has a first token iff its count > 0)
-    back.resize(N);
-    GEMHIP_REQUIRE(N > 0, "n2v_build_unigram_vocab_order: empty vocabulary");
-    std::vector<int32_t> cr(N), K;
-    std::vector<float> Uf;
-    for (int64_t r = 0; r < N; ++r) cr[r] = cnt[back[r]];
-    GEMHIP_REQUIRE(vose_unigram(cr.data(), N, 1, Uf, K), "n2v_build_unigram_vocab_order: empty vocabulary");
-    h->vs.build(cnt.data(), n);
-    std::vector<int32_t> slot(N);
-    std::vector<uint2> UK((size_t)n, make_uint2(0u, 0u));          // nodes that never occur are never drawn
-    for (int64_t r = 0; r < N; ++r) {
-        slot[r] = (flags & 2) ? back[K[r]] : back[r];
-        uint32_t ub; memcpy(&ub, &Uf[r], 4);
-        UK[back[r]] = make_uint2(ub, (uint32_t)back[K[r]]);
-    }
-    GEMHIP_CHECK(h->d_KTslot.reserve(n));
-    { PhaseScope ph(PH_H2D);
-      GEMHIP_CHECK(hipMemcpy(h->d_KTslot, slot.data(), N * sizeof(int32_t), hipMemcpyHostToDevice));
-      GEMHIP_CHECK(h->d_UK.upload(UK.data(), n)); }
+    GEMHIP_REQUIRE(host_tables(cnt, back.data(), 1, flags, T) < 0, "n2v_build_unigram_vocab_order: empty vocabulary");
+    if (int rc = upload_unigram(T, false, h->d_UT, h->d_KT, h->d_UK, h->d_KTslot)) return rc;
+    const int64_t N = T.n_vocab;
+    h->vs = std::move(T.vs);
     h->n_vocab = N; h->vocab_order = true; h->unigram_ready = true; h->sk_state = -1; h->hotkey_state = 0;
     if (n_vocab_out) *n_vocab_out = N;
-    if (order_out) std::copy(back.begin(), back.end(), order_out);
-    if (UT_out) std::copy(Uf.begin(), Uf.end(), UT_out);
-    if (KT_out) std::copy(K.begin(), K.end(), KT_out);
+    if (order_out) std::copy(back.begin(), back.begin() + N, order_out);
+    // the builder stores the table by node; entry r of the binary's table is node back[r], its alias the renamed id of that node's alias
+    if (UT_out) for (int64_t r = 0; r < N; ++r) UT_out[r] = T.U[back[r]];
+    if (KT_out) {
+        std::vector<int32_t> renamed(h->n, 0);
+        for (int64_t r = 0; r < N; ++r) renamed[back[r]] = (int32_t)r;
+        for (int64_t r = 0; r < N; ++r) KT_out[r] = renamed[T.K[back[r]]];
+    }
     return GEMHIP_OK;
 }
 
@@ -857,44 +766,21 @@ extern "C" int gemhip_n2v_build_unigram_vocab_order(gemhip_n2v_t h, int32_t flag
 extern "C" int gemhip_n2v_build_unigram_parts(gemhip_n2v_t h, int32_t parts, float *UT_out, int32_t *KT_out)
 {
     GEMHIP_REQUIRE(h && parts >= 1 && parts <= h->n, "n2v_build_unigram_parts: bad arguments");
-    GEMHIP_CHECK(hipDeviceSynchronize());
-    const int64_t n = h->n;
-    std::vector<int32_t> cnt(n);
-    GEMHIP_CHECK(hipMemcpy(cnt.data(), h->d_counts, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    h->vs.build(cnt.data(), (int64_t)cnt.size());
-    std::vector<float> Uall(n);
-    std::vector<int32_t> Kall(n);
-    h->part_off.assign(parts + 1, 0);
-    h->vs_part.assign(parts, VocabStats());
-    std::vector<int32_t> cp;
-    for (int32_t p = 0; p < parts; ++p) {
-        const int64_t np = (n - p + parts - 1) / parts;
-        h->part_off[p + 1] = h->part_off[p] + np;
-        std::vector<float> Uf; std::vector<int32_t> K;
-        GEMHIP_REQUIRE(vose_unigram(cnt.data() + p, np, parts, Uf, K), "n2v_build_unigram_parts: partition %d has an empty vocabulary", p);
-        std::copy(Uf.begin(), Uf.end(), Uall.begin() + h->part_off[p]);
-        std::copy(K.begin(), K.end(), Kall.begin() + h->part_off[p]);
-        cp.resize(np);
-        for (int64_t i = 0; i < np; ++i) cp[i] = cnt[p + i * parts];
-        h->vs_part[p].build(cp.data(), np);
-    }
-    GEMHIP_CHECK(h->d_UTp.upload(Uall.data(), n));
-    GEMHIP_CHECK(h->d_KTp.upload(Kall.data(), n));
-    {
-        std::vector<uint2> UK((size_t)n);
-        for (int64_t i = 0; i < n; ++i) { uint32_t ub; memcpy(&ub, &Uall[i], 4); UK[i] = make_uint2(ub, (uint32_t)Kall[i]); }
-        GEMHIP_CHECK(h->d_UKp.upload(UK.data(), n));
-    }
-    h->parts = parts; h->skp_state = -1; h->parts_vocab_order = false;
-    if (UT_out) std::copy(Uall.begin(), Uall.end(), UT_out);
-    if (KT_out) std::copy(Kall.begin(), Kall.end(), KT_out);
+    std::vector<int32_t> cnt; UnigramTables T;
+    if (int rc = read_counts(h, cnt)) return rc;
+    const int empty = host_tables(cnt, nullptr, parts, 0, T);
+    GEMHIP_REQUIRE(empty < 0, "n2v_build_unigram_parts: partition %d has an empty vocabulary", empty);
+    if (int rc = upload_unigram(T, true, h->d_UTp, h->d_KTp, h->d_UKp, h->d_KTslotp)) return rc;
+    if (UT_out) std::copy(T.U.begin(), T.U.end(), UT_out);
+    if (KT_out) std::copy(T.K.begin(), T.K.end(), KT_out);
+    commit_parts(h, T, parts, false);
     return GEMHIP_OK;
 }
 
 // The per-partition tables in the BINARY's layout (flags bit GEMHIP_N2V_VOCAB_ORDER on the N-GPU schedule): partition p = the nodes v % parts == p that
 // occur, in order of first appearance in the whole corpus -- d_corpus: the walks of ALL ranks in walk-id order (rank-major shards, -1 tokens = padding;
 // NULL = this handle's own walks: one rank) -- Vose over their counts (the handle's counts: summed over the ranks) in that order; the slot table and the
-// alias arrays are stored by LOCAL row v / parts like the node-id layout's.  With one partition this IS gemhip_n2v_build_unigram_vocab_order's table.
+// alias arrays are stored by LOCAL row v / parts like the node-id layout's.  With one partition this IS gemhip_n2v_build_unigram_vocab_order's table (the same call of the host builder).
 // Optional outputs: UT_out / KT_out [n] by local row (concatenated partitions, as d_UTp / d_KTp), slot_out [n] (partition p's slots at part_off[p],
 // -1 beyond its slot count), nslots_out [parts].
 extern "C" int gemhip_n2v_build_unigram_parts_vocab_order(gemhip_n2v_t h, int32_t parts, int32_t flags, const void *d_corpus, int64_t corpus_tokens,
@@ -902,53 +788,17 @@ extern "C" int gemhip_n2v_build_unigram_parts_vocab_order(gemhip_n2v_t h, int32_
 {
     GEMHIP_REQUIRE(h && parts >= 1 && parts <= h->n, "n2v_build_unigram_parts_vocab_order: bad arguments");
     GEMHIP_REQUIRE(d_corpus ? corpus_tokens > 0 : (h->d_walks && h->nwalks > 0), "n2v_build_unigram_parts_vocab_order: no walks");
-    const int64_t n = h->n;
-    std::vector<int32_t> back, cnt;
+    std::vector<int32_t> back, cnt; UnigramTables T;
     if (int rc = first_appearance_order(h, d_corpus ? (const int32_t *)d_corpus : h->d_walks, d_corpus ? corpus_tokens : h->nwalks * h->walk_len, back, cnt)) return rc;
-    int64_t N = 0;
-    while (N < n && cnt[back[N]] > 0) ++N;
-    GEMHIP_REQUIRE(N > 0, "n2v_build_unigram_parts_vocab_order: empty vocabulary");
-    h->vs.build(cnt.data(), n);
-    h->part_off.assign(parts + 1, 0);
-    h->vs_part.assign(parts, VocabStats());
-    h->part_slots.assign(parts, 0);
-    for (int32_t p = 0; p < parts; ++p) h->part_off[p + 1] = h->part_off[p] + (n - p + parts - 1) / parts;
-    std::vector<float> Uall(n, 0.f);
-    std::vector<int32_t> Kall(n, 0), Sall(n, -1), cp;
-    std::vector<std::vector<int32_t>> L(parts);                // partition p's occurring nodes in first-appearance order
-    for (int64_t r = 0; r < N; ++r) L[back[r] % parts].push_back(back[r]);
-    for (int32_t p = 0; p < parts; ++p) {
-        const int64_t off = h->part_off[p], np = h->part_off[p + 1] - off, Np = (int64_t)L[p].size();
-        GEMHIP_REQUIRE(Np > 0, "n2v_build_unigram_parts_vocab_order: partition %d has an empty vocabulary", p);
-        std::vector<int32_t> cr(Np), K; std::vector<float> Uf;
-        for (int64_t r = 0; r < Np; ++r) cr[r] = cnt[L[p][r]];
-        GEMHIP_REQUIRE(vose_unigram(cr.data(), Np, 1, Uf, K), "n2v_build_unigram_parts_vocab_order: partition %d has an empty vocabulary", p);
-        for (int64_t r = 0; r < Np; ++r) {
-            const int32_t loc = L[p][r] / parts, ali = L[p][K[r]] / parts;
-            Uall[off + loc] = Uf[r]; Kall[off + loc] = ali;
-            Sall[off + r] = (flags & 2) ? ali : loc;
-        }
-        h->part_slots[p] = Np;
-        cp.resize(np);
-        for (int64_t i = 0; i < np; ++i) cp[i] = cnt[p + i * parts];
-        h->vs_part[p].build(cp.data(), np);
-    }
-    {
-        PhaseScope ph(PH_H2D);
-        std::vector<uint2> UK((size_t)n);
-        for (int64_t i = 0; i < n; ++i) { uint32_t ub; memcpy(&ub, &Uall[i], 4); UK[i] = make_uint2(ub, (uint32_t)Kall[i]); }
-        std::vector<int32_t> Sdev(Sall);
-        for (auto &v : Sdev) if (v < 0) v = 0;                 // (never read: a partition's launches draw slots below its slot count)
-        GEMHIP_CHECK(h->d_UTp.upload(Uall.data(), n));
-        GEMHIP_CHECK(h->d_KTp.upload(Kall.data(), n));
-        GEMHIP_CHECK(h->d_UKp.upload(UK.data(), n));
-        GEMHIP_CHECK(h->d_KTslotp.upload(Sdev.data(), n));
-    }
-    h->parts = parts; h->skp_state = -1; h->parts_vocab_order = true;
-    if (UT_out) std::copy(Uall.begin(), Uall.end(), UT_out);
-    if (KT_out) std::copy(Kall.begin(), Kall.end(), KT_out);
-    if (slot_out) std::copy(Sall.begin(), Sall.end(), slot_out);
-    if (nslots_out) std::copy(h->part_slots.begin(), h->part_slots.end(), nslots_out);
+    const int empty = host_tables(cnt, back.data(), parts, flags, T);
+    GEMHIP_REQUIRE(T.n_vocab > 0, "n2v_build_unigram_parts_vocab_order: empty vocabulary");
+    GEMHIP_REQUIRE(empty < 0, "n2v_build_unigram_parts_vocab_order: partition %d has an empty vocabulary", empty);
+    if (int rc = upload_unigram(T, true, h->d_UTp, h->d_KTp, h->d_UKp, h->d_KTslotp)) return rc;
+    if (UT_out) std::copy(T.U.begin(), T.U.end(), UT_out);
+    if (KT_out) std::copy(T.K.begin(), T.K.end(), KT_out);
+    if (slot_out) std::copy(T.slot.begin(), T.slot.end(), slot_out);
+    if (nslots_out) std::copy(T.part_slots.begin(), T.part_slots.end(), nslots_out);
+    commit_parts(h, T, parts, true);
     return GEMHIP_OK;
 }
 
@@ -965,13 +815,6 @@ extern "C" int gemhip_sgns_init(gemhip_n2v_t h, int32_t d, uint64_t seed, void *
     const int64_t threads = (total + 3) / 4;
     hipLaunchKernelGGL(sgns_init_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, h->SynPos, h->SynNeg, total, d, seed);
     GEMHIP_CHECK(hipGetLastError());
-    return GEMHIP_OK;
-}
-
-extern "C" int gemhip_n2v_set_max_waves(gemhip_n2v_t h, int32_t max_waves)
-{
-    GEMHIP_REQUIRE(h && max_waves >= 0, "n2v_set_max_waves: bad arguments");
-    h->kn.max_waves = max_waves;
     return GEMHIP_OK;
 }
 
@@ -995,157 +838,20 @@ extern "C" int gemhip_sgns_get_tables(gemhip_n2v_t h, float *SynPos_host, float 
     return GEMHIP_OK;
 }
 
-// Which kernel, how many concurrent wavefronts and which rows are "hot" for one pass of TrainModel over `nwalks` walks.  Pure host arithmetic.
-//
-// Concurrency against quality -- the rule and where it comes from.  What Hogwild costs here is LOST UPDATES: every wavefront
-// keeps its 5 negative rows per pair open from their load to their store; a store another wavefront makes to such a row in between is
-// overwritten.  The CPU replay of this kernel's concurrency (scripts/hogwild_emul: W virtual wavefronts, the kernel's private copies) puts
-// ~90 % of the MAP loss on those overwritten negative-row updates, ~10 % on the centre row's, none on stale gradients; the expected fraction
-// of overwriting stores is  rho = W x 5 x w / n_eff  with w = the window in pair steps (prefetch + 1 without RELOAD; ~0.4 with it: one reload
-// round trip, ~0.5 us against a 1.35 us step) and n_eff = 1 / sum_v q_v^2 the EFFECTIVE table size of the negative-sampling distribution
-// (unigram^0.75): n on a graph whose nodes are equally frequent (SBM: n / 1.06), far smaller on a power-law graph (R-MAT scale 17: 11 316 of
-// 131 072 nodes).  Measured at SBM 1M/10M against the sequential oracle (same seed, paired per-node AP): without RELOAD rho = 1.1 % / 1.5 % /
-// 2.3 % (768 / 1024 / 1536 wavefronts) cost -0.1 % / -0.4..-0.9 % / -0.8..-1.3 % of MAP, and 1536 wavefronts with prefetch 1 (rho 1.5 %)
-// -0.5 %: the loss follows rho, not the wavefront count; with RELOAD 1536 wavefronts (rho 0.3 %) measure +0.15 +- 0.25 %.  Default: rho <= 1.5 %.
-static SgnsLaunchPlan plan_sgns_launch(const VocabStats &vs, const SgnsKnobs &kn, int64_t n, int32_t d, int32_t window, int32_t walk_len,
-                                       int64_t nwalks, int32_t flags)
-{
-    SgnsLaunchPlan P;
-    const bool deterministic = (flags & 4) != 0;
-    // window-cached kernel (default): radius R = tokens either side of the centre whose SynPos row stays in LDS
-    int R = kn.cache_radius < 0 ? 10 : kn.cache_radius;
-    R = std::min(R, std::min(window, 31));
-    const int rw = sgns_win_row_floats(d);
-    const size_t ints = (size_t)((walk_len + 4 * window * SGNS_NEG + 3) & ~3);
-    // tokens + negative targets of two centres, the window rows (twice with the delta write-back: as trained / as loaded) and -- unless every context
-    // row is cached (`allc`: R >= window and no hot rows, the launcher's ALLC instantiations) -- one staging row for an uncached context
-    // (kn.part: the bucket kernels keep the as-loaded copies in a global scratch instead of LDS)
-    auto lds_bytes = [&](bool delta, bool allc) { return ints * sizeof(int32_t) + (size_t)((2 * R + 1) * ((delta && !kn.part) ? 2 : 1) + (allc ? 0 : 1)) * rw * sizeof(float); };
-    // the window has to fit a block's LDS: wide rows / long walks fall back to sgns_kernel
-    P.window = R > 0 && !(flags & GEMHIP_N2V_NO_WINDOW_CACHE) && 2 * window * SGNS_NEG <= 2 * WAVE && walk_len >= 2 && lds_bytes(true, false) <= 64 * 1024 &&
-               (d % 2 == 0 ? d <= 512 : d <= 256);
-    if (!P.window) {
-        // sgns_kernel: four wavefronts per workgroup, no private copies beyond the pair in flight.  Small graphs: when the open rows approach n,
-        // concurrent writers overwrite each other's updates and the embedding degrades (tests/test_n2v_gpu.py): n / 128 wavefronts
-        const size_t per_wave = (size_t)(walk_len + 2 * window * SGNS_NEG) * sizeof(int32_t);
-        if (!deterministic) {
-            const int64_t hog_cap = kn.max_waves > 0 ? kn.max_waves : std::max<int64_t>(1, n / HOGWILD_ROWS_PER_WAVE);
-            P.waves = std::min<int64_t>(std::min<int64_t>(hog_cap, 256 * 16), nwalks);          // 16 waves/CU already saturate the fabric (scripts/ab_sgns_waves.py)
-            P.threads = 256; P.blocks = (int)((P.waves + 3) / 4);
-        }
-        P.lds = per_wave * (P.threads / 64);
-        return P;
-    }
-    P.R = R;
-    const int mode = kn.cache_delta;                 // -1 auto: delta write-back whenever other wavefronts train concurrently
-    P.delta = deterministic && mode == 1;            // (cache_delta 1 on a deterministic launch: the Hogwild code path on ONE wavefront, for the parity tests)
-    // a node expected to sit in another wavefront's window at any time -- (W - 1) x (2R + 1) x count / tokens >= 1 -- is hot
-    const double span = kn.window_span > 0 ? (double)kn.window_span : (double)(2 * R + 1);
-    auto hot_threshold = [&](int64_t waves) -> int32_t {
-        if (kn.hot_count > 0) return kn.hot_count;
-        if (kn.hot_count < 0 && waves > 1 && vs.total > 0.0) {
-            const double thr = vs.total / ((double)(waves - 1) * span);
-            if (vs.max >= thr) return (int32_t)std::max(2.0, std::ceil(thr));
-        }
-        return 0;
-    };
-    bool allc = R >= window && !kn.has_local_hot;
-    if (!deterministic) {
-        P.delta = mode != 0;
-        // the (reload, prefetch) pair the launcher will actually run: launches WITHOUT reload-on-update and with prefetch distance 1 exist for the
-        // benchmark shape only (d == 128, whole window cached, no hot rows -- launch_sgns_win's AB instantiations); every other Hogwild launch is
-        // reload-on-update with prefetch distance 2 whatever the knobs say, and the width rule has to be computed for THAT kernel
-        auto w_steps_of = [&](bool all_cached) -> double {
-            const bool ab_shape = d == 128 && all_cached;
-            const bool reload_eff = P.delta && (kn.reload || !ab_shape);
-            return reload_eff ? 0.4 : (double)((ab_shape ? kn.prefetch : 2) + 1);
-        };
-        const double n_eff = vs.n_eff > 0.0 ? vs.n_eff : (double)n;
-        // graphs below 8192 nodes: the window rows themselves (2R+1 per wavefront) are a sizeable part of the table -- SBM-1024 (d=16) loses
-        // 3.5 % of MAP at 8 wavefronts and nothing at 2: bound the open fraction of the table at 1/16
-        const int64_t hog_tiny = std::max<int64_t>(1, n / (16 * (8 + 2 * R + 1)));
-        // ... but never more wavefronts than 2 % of the rows that occur at all: that is as far as the measurements behind this rule reach (stale
-        // gradients cost nothing up to there -- CPU replay at 0.4 %, SBM 100k at 0.8 %, R-MAT scale 17 at 2.0 % of the active rows; R-MAT scale 13 with
-        // 26 % of its 5 936 active rows open ended 21 % ABOVE the sequential algorithm's MAP: its hubs under-trained)
-        const int64_t w_act = std::max<int64_t>(1, (int64_t)((vs.active > 0.0 ? vs.active : (double)n) / 50.0));
-        // ... and, on graphs with hubs, never more than the CONCURRENT-TOUCH bound of round 5: (W - 1) x touch2_hub <= 0.165, touch2_hub = the hubs' part of
-        // sum_v (p_v + 5 q_v)^2 (p = token share: the context; q = unigram^0.75 share: the five negatives) -- minus the 40 / active a table of equally frequent
-        // rows has, so that SBM graphs stay on the rho rule they were validated on.  What round 6 found out about it (profiles/r06_*.jsonl):
-        //  * the bound was fitted through launches whose gaps were dominated by a HEAVY TAIL that has nothing to do with hubs: an isolated edge trained by two
-        //    wavefronts at once (LOCALLY HOT ROWS, ensure_hotkey below -- now handled; launches at one width agree to 0.2 % where they scattered over 6 %);
-        //  * the staleness of the hubs' gradients is not the cause either: instrumented (GEMHIP_SGNS_STALENESS), the top hub's row takes 22 foreign updates
-        //    between a wavefront's read and its add at 768 wavefronts; fresh reads / returning atomics cut that to 6 and the gap does not move; making every
-        //    Hogwild write a lossless add makes it slightly WORSE; lowering the hot-row threshold 2-16x makes it worse and slower;
-        //  * what is left is smooth in the width and larger on the larger graph -- R-MAT scale 17: -0.45 / -1.6 / -1.8 % at 256 / 768 / 1 536 wavefronts, scale 20:
-        //    -1.3 / -3.0 / -6.0 % (paired with the sequential oracle, s.e. 0.3-0.5 %, 2-4 launches each) -- carried by query nodes of 1 000..30 000 tokens, and
-        //    slower launches of the same configuration are the worse ones (queueing of the hot rows' atomic adds at the memory side is the suspect).
-        // So the bound stays as the conservative extrapolation it is (548 wavefronts on scale 22 -- both oracle runs exist since round 6, their scoring did not finish: no pin yet), with a
-        // FLOOR of 256 wavefronts: at 256 both measured graphs are at or inside -1.3 % (round 5's 50 wavefronts on scale 17 bought nothing for 3.5x the time:
-        // ADVICE r5), and ONE bound for both unigram-table layouts -- round 5 halved it for the node-id layout on the strength of two launches (-6.3 % at 207
-        // wavefronts) that the heavy tail explains; after the fix the layouts measure alike (scale 20, 768 wavefronts: -2.7 / -3.3 % and -2.5 / -4.3 %).
-        const double touch_bound = 0.165;
-        const double touch2_hub = std::max(0.0, vs.touch2 - 40.0 / std::max(1.0, vs.active > 0.0 ? vs.active : (double)n));
-        const int64_t w_touch = touch2_hub > 0.0 ? std::max<int64_t>(256, 1 + (int64_t)std::min(1e15, touch_bound / (touch2_hub * kn.touch_scale))) : INT64_MAX;
-        auto width = [&](bool all_cached) -> int64_t {
-            // registers: the single-GPU kernels allocate 176-184 VGPRs (2 wavefronts per SIMD = 8 per CU), the bucket kernels 136-145 (3 per SIMD = 12 per CU)
-            const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kn.part ? 12 : 8, (int64_t)(160 * 1024) / (int64_t)(lds_bytes(P.delta, all_cached) + 512)));
-            const int64_t w_dev = std::min<int64_t>(256 * per_cu, nwalks);
-            const double w_steps = w_steps_of(all_cached);
-            const bool reload_eff = w_steps < 1.0;
-            int64_t hog_rho = std::max<int64_t>(1, (int64_t)(0.015 * n_eff / (5.0 * w_steps * kn.duty)));
-            // hot rows: with W wavefronts the nodes with count >= tokens / ((W-1)(2R+1)) stay out of the LDS windows and take their negative updates
-            // by atomic add (sgns_win_kernel), so the rule only has to hold over the remaining (cold) rows: the largest W that satisfies it
-            if (reload_eff && kn.hot_count < 0 && n >= 8192 && hog_rho < std::min(std::min(w_dev, w_act), w_touch) && vs.total > 0.0) {
-                for (int64_t wtry = std::min(std::min(w_dev, w_act), w_touch); wtry > hog_rho; wtry = wtry * 7 / 8) {
-                    const double thr = std::max(2.0, std::ceil(vs.total / ((double)(wtry - 1) * span)));
-                    if (0.015 * vs.n_eff_cold(thr) / (5.0 * w_steps * kn.duty) >= (double)wtry) { hog_rho = wtry; break; }
-                }
-            }
-            const int64_t hog_win = kn.max_waves > 0 ? kn.max_waves : n >= 8192 ? std::min(hog_rho, w_touch) : std::min(hog_rho, hog_tiny);
-            int64_t w = std::min<int64_t>(hog_win, w_dev);
-            // Speed only (round 5): hot rows are updated by atomic adds at the memory side, and those saturate long before the device's wavefront slots do:
-            // past ~three wavefronts per CU more wavefronts only queue up behind the same rows and touch them more often at once.  Measured per SGNS launch,
-            // same box each (profiles/r05_rmat22_width_sweep.jsonl, r05_rmat20_width_sweep.jsonl): R-MAT scale 22 41.3 / 33.0 / 34.3 / 36.7 s and scale 20
-            // 12.5 / 10.3 / 10.7 / 15.0 s at 512 / 768 / 1024 / 1536 wavefronts.  (A rate model -- min(W / wave step, atomic row operations per second / hot
-            // operations per pair) -- fitted scale 22 and 17 and then put scale 20 at 496 wavefronts, 25 % slower than 768: the atomic unit's rate is not a
-            // constant of the device, it grows with the number of distinct hot rows.  Dropped for the plain cap.)  Widths only ever shrink here.
-            if (kn.max_waves == 0 && !kn.part && reload_eff && kn.hot_count < 0 && n >= 8192 && w > 768 && vs.total > 0.0 &&
-                vs.max >= std::max(2.0, std::ceil(vs.total / ((double)(w - 1) * span))))
-                w = 768;
-            return w;
-        };
-        // the launch without the staging row holds one more wavefront per CU at d = 128 -- but only exists when no row is hot AT THAT WIDTH
-        P.waves = width(allc);
-        if (allc && hot_threshold(P.waves) != 0) { allc = false; P.waves = width(false); }
-        if (P.waves == 1 && mode < 0) P.delta = false;
-    }
-    P.hot_thr = hot_threshold(P.waves);
-    if (P.hot_thr == 0 && kn.has_local_hot && P.delta && P.waves > 1) P.hot_thr = INT32_MAX;       // only the locally hot nodes (hotkey INT32_MAX) qualify
-    // (the launcher takes an ALLC instantiation iff R >= window && hot_thr == 0: `allc` false with hot_thr 0 only gives that kernel a row it does not use)
-    P.lds = lds_bytes(P.delta, allc && P.hot_thr == 0);
-    P.blocks = (int)P.waves; P.threads = 64;
-    return P;
-}
-
 // LOCALLY HOT ROWS: the array the Hogwild kernels compare with hot_thr -- the token count, or INT32_MAX for a node whose tokens are packed into few walks
-// (kernels above).  Built on `stream` from the walks this handle holds and its (possibly externally reduced) counts; rebuilt after walks / vocabulary
-// change.  n_local_hot is read back (one 4-byte copy): a launch without any such node and without count-hot rows keeps the all-cached instantiation.
-static int ensure_hotkey_buffers(gemhip_n2v_t h)
+// (kernels above).  Built on `stream` from `rows` walks of walk_len tokens (rows of -1 tokens count nothing) and the handle's (possibly externally
+// reduced) counts; n_local_hot is read back (one 4-byte copy): a launch without any such node and without count-hot rows keeps the all-cached
+// instantiation.  state: what hotkey_state becomes -- 1 built from the handle's own walks, 2 from a gathered corpus.
+static int build_hotkey(gemhip_n2v_t h, const int32_t *walks, int64_t rows, int32_t walk_len, hipStream_t stream, int state)
 {
     GEMHIP_CHECK(h->d_hotkey.reserve(h->n));
     GEMHIP_CHECK(h->d_wcount.reserve(h->n));
     GEMHIP_CHECK(h->d_nlocal.reserve(1));
-    return GEMHIP_OK;
-}
-static int ensure_hotkey(gemhip_n2v_t h, hipStream_t stream)
-{
-    if (h->hotkey_state == 1) return GEMHIP_OK;
-    if (int rc = ensure_hotkey_buffers(h)) return rc;
     GEMHIP_CHECK(hipMemsetAsync(h->d_wcount, 0, (size_t)h->n * sizeof(int32_t), stream));
     GEMHIP_CHECK(hipMemsetAsync(h->d_nlocal, 0, sizeof(unsigned int), stream));
-    if (h->nwalks > 0) {
-        const int64_t blocks = std::min<int64_t>(h->nwalks, 256 * 32);
-        hipLaunchKernelGGL(n2v_walk_presence_kernel, dim3((unsigned)blocks), dim3(64), (size_t)h->walk_len * sizeof(int32_t), stream, h->d_walks, h->nwalks, h->walk_len, h->d_wcount);
+    if (rows > 0) {
+        const int64_t blocks = std::min<int64_t>(rows, 256 * 32);
+        hipLaunchKernelGGL(n2v_walk_presence_kernel, dim3((unsigned)blocks), dim3(64), (size_t)walk_len * sizeof(int32_t), stream, walks, rows, walk_len, h->d_wcount);
     }
     hipLaunchKernelGGL(n2v_hotkey_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, stream, h->n, h->d_counts, h->d_wcount, h->kn.local_hot, h->d_hotkey, h->d_nlocal);
     GEMHIP_CHECK(hipGetLastError());
@@ -1153,8 +859,13 @@ static int ensure_hotkey(gemhip_n2v_t h, hipStream_t stream)
     GEMHIP_CHECK(hipMemcpyAsync(&nl, h->d_nlocal, sizeof nl, hipMemcpyDeviceToHost, stream));
     GEMHIP_CHECK(hipStreamSynchronize(stream));
     h->n_local_hot = nl;
-    h->hotkey_state = 1;
+    h->hotkey_state = state;
     return GEMHIP_OK;
+}
+// ... of the walks this handle holds: rebuilt after walks / vocabulary change
+static int ensure_hotkey(gemhip_n2v_t h, hipStream_t stream)
+{
+    return h->hotkey_state == 1 ? GEMHIP_OK : build_hotkey(h, h->d_walks, h->nwalks, h->walk_len, stream, 1);
 }
 
 // The slot table the window kernels draw negatives from (SgnsArgs::SK), for the table currently held and the given quirk bit.  Built on `stream`,
@@ -1200,6 +911,96 @@ static int ensure_win_scratch(gemhip_n2v_t h, const SgnsLaunchPlan &P, int32_t d
     return GEMHIP_OK;
 }
 
+// Instrumentation builds (scripts/build_variant.sh with -DGEMHIP_SGNS_STALENESS / -DGEMHIP_SGNS_PROFILE): device counters a window launch of
+// gemhip_sgns_train carries (begin) and the line printed once it has run (report).  The product build compiles neither.
+#ifdef GEMHIP_SGNS_STALENESS
+static int staleness_begin(gemhip_n2v_t h, SgnsArgs &A)
+{
+    static unsigned int *d_sver = nullptr; static unsigned long long *d_shist = nullptr; static int64_t sver_n = 0;
+    if (sver_n < h->n) { if (d_sver) hipFree(d_sver); GEMHIP_CHECK(hipMalloc(&d_sver, (size_t)h->n * 2 * sizeof(unsigned int))); sver_n = h->n; }
+    if (!d_shist) GEMHIP_CHECK(hipMalloc(&d_shist, 3 * 32 * 16 * sizeof(unsigned long long)));
+    GEMHIP_CHECK(hipMemset(d_sver, 0, (size_t)h->n * 2 * sizeof(unsigned int)));
+    GEMHIP_CHECK(hipMemset(d_shist, 0, 3 * 32 * 16 * sizeof(unsigned long long)));
+    A.stale_ver = d_sver; A.stale_hist = d_shist;
+    return GEMHIP_OK;
+}
+// one JSON line per launch: {"waves", "hot_thr", "fresh", "hist": {class: {log2 count: [launches by bit length of the foreign-update count]}}}
+static int staleness_report(gemhip_n2v_t h, const SgnsLaunchPlan &P, const SgnsArgs &A)
+{
+    std::vector<unsigned long long> hh(3 * 32 * 16);
+    GEMHIP_CHECK(hipDeviceSynchronize());
+    GEMHIP_CHECK(hipMemcpy(hh.data(), A.stale_hist, hh.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    FILE *fo = getenv("GEMHIP_SGNS_STALENESS_OUT") ? fopen(getenv("GEMHIP_SGNS_STALENESS_OUT"), "a") : stderr;
+    if (fo) {
+        fprintf(fo, "{\"waves\": %lld, \"hot_thr\": %d, \"fresh\": %d, \"vocab_order\": %d, \"hist\": {", (long long)P.waves, (int)P.hot_thr, (int)A.fresh, (int)h->vocab_order);
+        const char *cls[3] = {"negative", "centre", "context"};
+        for (int c = 0; c < 3; ++c) {
+            fprintf(fo, "%s\"%s\": {", c ? ", " : "", cls[c]);
+            bool first = true;
+            for (int hb = 0; hb < 32; ++hb) {
+                unsigned long long tot = 0; for (int sb = 0; sb < 16; ++sb) tot += hh[(c * 32 + hb) * 16 + sb];
+                if (!tot) continue;
+                fprintf(fo, "%s\"%d\": [", first ? "" : ", ", hb); first = false;
+                for (int sb = 0; sb < 16; ++sb) fprintf(fo, "%s%llu", sb ? ", " : "", hh[(c * 32 + hb) * 16 + sb]);
+                fprintf(fo, "]");
+            }
+            fprintf(fo, "}");
+        }
+        fprintf(fo, "}}\n");
+        if (fo != stderr) fclose(fo);
+    }
+    return GEMHIP_OK;
+}
+#else
+static int staleness_begin(gemhip_n2v_t, SgnsArgs &) { return GEMHIP_OK; }
+static int staleness_report(gemhip_n2v_t, const SgnsLaunchPlan &, const SgnsArgs &) { return GEMHIP_OK; }
+#endif
+#ifdef GEMHIP_SGNS_PROFILE
+static int profile_begin(SgnsArgs &A)
+{
+    static unsigned long long *d_prof = nullptr;
+    if (!d_prof) GEMHIP_CHECK(hipMalloc(&d_prof, 64));
+    GEMHIP_CHECK(hipMemset(d_prof, 0, 64));
+    A.prof = d_prof;
+    return GEMHIP_OK;
+}
+static int profile_report(const SgnsLaunchPlan &P, const SgnsArgs &A)
+{
+    unsigned long long hp[8];
+    GEMHIP_CHECK(hipDeviceSynchronize());
+    GEMHIP_CHECK(hipMemcpy(hp, A.prof, 64, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[sgns profile] waves=%lld cycles: other=%llu issue=%llu ctx_lds=%llu wait_rows=%llu compute_store=%llu neg_pipeline=%llu centre_setup=%llu centre_end=%llu\n",
+            (long long)P.waves, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7]);
+    return GEMHIP_OK;
+}
+#else
+static int profile_begin(SgnsArgs &) { return GEMHIP_OK; }
+static int profile_report(const SgnsLaunchPlan &, const SgnsArgs &) { return GEMHIP_OK; }
+#endif
+
+// What gemhip_sgns_train and gemhip_sgns_train_part hand the kernels alike (every other field keeps SgnsArgs' default until its entry point sets it): the
+// walks and the range of work items, alpha's schedule, the Philox keys, the embedding tables, the handle's pair counter and fresh-row knobs, and the
+// unigram table the negatives are drawn from -- the handle's single table (word_part < 0) or the one of partition word_part, in the layout it was built in
+static SgnsArgs sgns_args(gemhip_n2v_t h, int32_t word_part, const int32_t *walks, int64_t walk_lo, int64_t walk_hi, int32_t walk_len, int32_t window, float alpha0,
+                          int64_t denom, int64_t token_offset, int64_t walk_id_offset, int32_t epoch, uint64_t seed, int32_t flags, int32_t d, float *SynPos, float *SynNeg)
+{
+    SgnsArgs A;
+    A.walks = walks; A.walk_lo = walk_lo; A.walk_hi = walk_hi; A.walk_len = walk_len; A.window = window;
+    // the kernel computes t = token_offset + wl*walk_len + pos with wl the index of the work item
+    A.alpha0 = alpha0; A.denom = denom; A.token_offset = token_offset; A.walk_id_offset = walk_id_offset; A.epoch = epoch;
+    A.seed = seed; A.flags = flags; A.d = d;
+    const bool part = word_part >= 0;
+    const int64_t off = part ? h->part_off[word_part] : 0;
+    A.UT = (part ? h->d_UTp : h->d_UT) + off; A.KT = (part ? h->d_KTp : h->d_KT) + off; A.UK = (part ? h->d_UKp : h->d_UK) + off;
+    A.n = (uint32_t)(part ? h->part_off[word_part + 1] - off : h->n);
+    if (part ? h->parts_vocab_order : h->vocab_order) {      // the binary's table layout: slots over the (partition's) nodes that occur, in first-appearance order; the slot table is always consulted
+        A.KT = (part ? h->d_KTslotp : h->d_KTslot) + off; A.n = (uint32_t)(part ? h->part_slots[word_part] : h->n_vocab); A.flags = flags | 2; A.UT = nullptr;
+    }
+    A.SynPos = SynPos; A.SynNeg = SynNeg; A.pairs = h->d_pairs;
+    A.fresh = h->kn.fresh; A.neg_thr = h->kn.neg_count; A.n_nodes = h->n;
+    return A;
+}
+
 extern "C" int gemhip_sgns_train(gemhip_n2v_t h, int32_t window, int32_t neg, float alpha0, int32_t epochs, int32_t epoch,
                                  int64_t walk_lo, int64_t walk_hi, int64_t tokens_total, int64_t token_offset, uint64_t seed,
                                  int32_t flags, void *stream)
@@ -1212,20 +1013,9 @@ extern "C" int gemhip_sgns_train(gemhip_n2v_t h, int32_t window, int32_t neg, fl
     GEMHIP_REQUIRE(0 <= walk_lo && walk_lo <= walk_hi && walk_hi <= h->nwalks, "sgns_train: bad local walk range");
     GEMHIP_REQUIRE(tokens_total >= 1, "sgns_train: tokens_total=%lld", (long long)tokens_total);
     if (walk_hi == walk_lo) return GEMHIP_OK;
-    SgnsArgs A;
-    A.walks = h->d_walks; A.walk_lo = walk_lo; A.walk_hi = walk_hi; A.walk_len = h->walk_len; A.window = window;
-    A.alpha0 = alpha0; A.denom = (int64_t)epochs * tokens_total + 1;
-    // the kernel computes t = token_offset + wl*walk_len + pos with wl the LOCAL walk index
-    A.token_offset = token_offset; A.walk_id_offset = h->walk_id_offset; A.epoch = epoch;
-    A.UT = h->d_UT; A.KT = h->d_KT; A.UK = h->d_UK; A.n = (uint32_t)h->n; A.seed = seed; A.flags = flags; A.d = h->d;
-    if (h->vocab_order) {      // the binary's table layout: slots over the nodes that occur, in first-appearance order; the slot table is always consulted
-        A.KT = h->d_KTslot; A.n = (uint32_t)h->n_vocab; A.flags = flags | 2; A.UT = nullptr;
-    }
-    A.SK = nullptr;
-    A.SynPos = h->SynPos; A.SynNeg = h->SynNeg; A.pairs = h->d_pairs;
-    A.dummy = nullptr; A.prof = nullptr; A.cache_radius = 0; A.nwaves = 1; A.prefetch = h->kn.prefetch; A.reload = h->kn.reload; A.counts = nullptr; A.hot_thr = 0;
-    A.parts = 0; A.ctx_part = 0; A.word_part = 0; A.seg = nullptr; A.nseg = 0; A.seg_len = 0; A.scratch = nullptr;
-    A.fresh = h->kn.fresh; A.neg_thr = h->kn.neg_count; A.stale_ver = nullptr; A.stale_hist = nullptr; A.n_nodes = h->n;
+    SgnsArgs A = sgns_args(h, -1, h->d_walks, walk_lo, walk_hi, h->walk_len, window, alpha0, (int64_t)epochs * tokens_total + 1, token_offset, h->walk_id_offset,
+                           epoch, seed, flags, h->d, h->SynPos, h->SynNeg);
+    A.prefetch = h->kn.prefetch; A.reload = h->kn.reload;
     SgnsKnobs kn_launch = h->kn;
     kn_launch.node_id_layout = !h->vocab_order;
     // LOCALLY HOT ROWS need the WHOLE corpus on this handle (walks-per-node is a property of the corpus: a rank's shard against all-reduced counts would
@@ -1245,61 +1035,18 @@ extern "C" int gemhip_sgns_train(gemhip_n2v_t h, int32_t window, int32_t neg, fl
         // LOCALLY HOT ROWS: the kernel compares `hotkey` (INT32_MAX for a node whose tokens are packed into few walks, else its token count) with the threshold
         if (P.delta && P.waves > 1 && kn_launch.has_local_hot) A.counts = h->d_hotkey;
         { const int rc = ensure_win_scratch(h, P, h->d, false, A); if (rc) return rc; }
-#ifdef GEMHIP_SGNS_STALENESS
-        static unsigned int *d_sver = nullptr; static unsigned long long *d_shist = nullptr; static int64_t sver_n = 0;
-        if (sver_n < h->n) { if (d_sver) hipFree(d_sver); GEMHIP_CHECK(hipMalloc(&d_sver, (size_t)h->n * 2 * sizeof(unsigned int))); sver_n = h->n; }
-        if (!d_shist) GEMHIP_CHECK(hipMalloc(&d_shist, 3 * 32 * 16 * sizeof(unsigned long long)));
-        GEMHIP_CHECK(hipMemset(d_sver, 0, (size_t)h->n * 2 * sizeof(unsigned int)));
-        GEMHIP_CHECK(hipMemset(d_shist, 0, 3 * 32 * 16 * sizeof(unsigned long long)));
-        A.stale_ver = d_sver; A.stale_hist = d_shist;
-#endif
-#ifdef GEMHIP_SGNS_PROFILE
-        static unsigned long long *d_prof = nullptr;
-        if (!d_prof) GEMHIP_CHECK(hipMalloc(&d_prof, 64));
-        GEMHIP_CHECK(hipMemset(d_prof, 0, 64));
-        A.prof = d_prof;
-#endif
+        if (int rc = staleness_begin(h, A)) return rc;
+        if (int rc = profile_begin(A)) return rc;
     }
     sgns_fn fn = !P.window ? pick_sgns(h->d) : P.delta ? pick_sgns_win_hogwild(h->d) : pick_sgns_win_det(h->d);
     GEMHIP_REQUIRE(fn != nullptr, "sgns_train: d=%d unsupported", h->d);
     h->last_plan = P; h->last_fresh = (P.window && P.delta && P.hot_thr > 0) ? A.fresh : 0;
     fn(A, P.blocks, P.threads, P.lds, (hipStream_t)stream);
     GEMHIP_CHECK(hipGetLastError());
-#ifdef GEMHIP_SGNS_STALENESS
-    if (P.window) {      // one JSON line per launch: {"waves", "hot_thr", "fresh", "hist": {class: {log2 count: [launches by bit length of the foreign-update count]}}}
-        std::vector<unsigned long long> hh(3 * 32 * 16);
-        GEMHIP_CHECK(hipDeviceSynchronize());
-        GEMHIP_CHECK(hipMemcpy(hh.data(), A.stale_hist, hh.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        FILE *fo = getenv("GEMHIP_SGNS_STALENESS_OUT") ? fopen(getenv("GEMHIP_SGNS_STALENESS_OUT"), "a") : stderr;
-        if (fo) {
-            fprintf(fo, "{\"waves\": %lld, \"hot_thr\": %d, \"fresh\": %d, \"vocab_order\": %d, \"hist\": {", (long long)P.waves, (int)P.hot_thr, (int)A.fresh, (int)h->vocab_order);
-            const char *cls[3] = {"negative", "centre", "context"};
-            for (int c = 0; c < 3; ++c) {
-                fprintf(fo, "%s\"%s\": {", c ? ", " : "", cls[c]);
-                bool first = true;
-                for (int hb = 0; hb < 32; ++hb) {
-                    unsigned long long tot = 0; for (int sb = 0; sb < 16; ++sb) tot += hh[(c * 32 + hb) * 16 + sb];
-                    if (!tot) continue;
-                    fprintf(fo, "%s\"%d\": [", first ? "" : ", ", hb); first = false;
-                    for (int sb = 0; sb < 16; ++sb) fprintf(fo, "%s%llu", sb ? ", " : "", hh[(c * 32 + hb) * 16 + sb]);
-                    fprintf(fo, "]");
-                }
-                fprintf(fo, "}");
-            }
-            fprintf(fo, "}}\n");
-            if (fo != stderr) fclose(fo);
-        }
-    }
-#endif
-#ifdef GEMHIP_SGNS_PROFILE
     if (P.window) {
-        unsigned long long hp[8];
-        GEMHIP_CHECK(hipDeviceSynchronize());
-        GEMHIP_CHECK(hipMemcpy(hp, A.prof, 64, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[sgns profile] waves=%lld cycles: other=%llu issue=%llu ctx_lds=%llu wait_rows=%llu compute_store=%llu neg_pipeline=%llu centre_setup=%llu centre_end=%llu\n",
-                (long long)P.waves, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7]);
+        if (int rc = staleness_report(h, P, A)) return rc;
+        if (int rc = profile_report(P, A)) return rc;
     }
-#endif
     return GEMHIP_OK;
 }
 
@@ -1313,7 +1060,7 @@ extern "C" int gemhip_sgns_plan_launch(const int32_t *counts, int64_t n, int32_t
     SgnsKnobs kn;
     kn.node_id_layout = !(flags & GEMHIP_N2V_VOCAB_ORDER);
     const SgnsLaunchPlan P = plan_sgns_launch(vs, kn, n, d, window, walk_len, nwalks, flags);
-    if (kernel) *kernel = !P.window ? 0 : P.delta ? 2 : 1;          // 0 sgns_kernel, 1 sgns_win_kernel (overwrite on leave), 2 sgns_win_kernel (Hogwild: delta write-back)
+    if (kernel) *kernel = P.kernel();
     if (waves) *waves = (int32_t)P.waves;
     if (hot_threshold) *hot_threshold = P.hot_thr;
     if (n_eff) *n_eff = vs.n_eff;
@@ -1341,44 +1088,14 @@ extern "C" int gemhip_sgns_train_part(gemhip_n2v_t h, const void *d_walks, int64
                    nseg, (long long)seg_len, (long long)nwalks);
     GEMHIP_REQUIRE((h->n + h->parts - 1) / h->parts < (int64_t)(1 << 29), "sgns_train_part: more than 2^29 rows per partition");
     if (nwalks == 0) return GEMHIP_OK;
-    SgnsArgs A;
-    A.walks = (const int32_t *)d_walks; A.walk_lo = 0; A.walk_hi = nwalks; A.walk_len = walk_len; A.window = window;
-    A.alpha0 = alpha0; A.denom = alpha_tokens_total + 1; A.token_offset = token_offset; A.walk_id_offset = walk_id_offset; A.epoch = epoch;
-    const int64_t off = h->part_off[word_part];
-    A.UT = h->d_UTp + off; A.KT = h->d_KTp + off; A.UK = h->d_UKp + off; A.n = (uint32_t)(h->part_off[word_part + 1] - off);
-    A.seed = seed; A.flags = flags; A.d = d;
-    if (h->parts_vocab_order) {        // the binary's layout: slots over the partition's nodes that occur; the slot table is always consulted
-        A.KT = h->d_KTslotp + off; A.n = (uint32_t)h->part_slots[word_part]; A.flags = flags | 2; A.UT = nullptr;
-    }
-    { const int rc = ensure_slot_table_parts(h, (A.flags & 2) ? 1 : 0, (hipStream_t)stream); if (rc) return rc; }
-    A.SK = h->d_SKp + off;
-    A.SynPos = (float *)dSynPos_part; A.SynNeg = (float *)dSynNeg_part; A.pairs = h->d_pairs;
-    A.dummy = nullptr; A.prof = nullptr; A.prefetch = 2; A.reload = 1; A.counts = h->d_counts; A.hot_thr = 0;
+    SgnsArgs A = sgns_args(h, word_part, (const int32_t *)d_walks, 0, nwalks, walk_len, window, alpha0, alpha_tokens_total + 1, token_offset, walk_id_offset, epoch, seed,
+                           flags, d, (float *)dSynPos_part, (float *)dSynNeg_part);
+    if (int rc = ensure_slot_table_parts(h, (A.flags & 2) ? 1 : 0, (hipStream_t)stream)) return rc;
+    A.SK = h->d_SKp + h->part_off[word_part];
+    A.counts = h->d_counts;
     A.parts = h->parts; A.ctx_part = ctx_part; A.word_part = word_part; A.seg = (const int64_t *)d_seg; A.nseg = nseg; A.seg_len = seg_len;
-    A.fresh = h->kn.fresh; A.neg_thr = h->kn.neg_count; A.stale_ver = nullptr; A.stale_hist = nullptr; A.n_nodes = h->n;
-    // the launch rule of gemhip_sgns_train on the rows in play: the negative rows are those of partition word_part (n_eff of ITS restricted unigram
-    // distribution bounds the Hogwild width: rho = W x 5 x 0.4 / n_eff <= 1.5 %); hot rows are judged on the GLOBAL token counts (a hub sits in
-    // W x (2R+1) x count / tokens windows whatever partition it belongs to)
-    VocabStats vs = h->vs_part[word_part];
-    vs.total = h->vs.total; vs.max = h->vs.max; vs.touch2 = h->vs.touch2;
-    SgnsKnobs kn = h->kn;
-    kn.prefetch = 2; kn.reload = 1; kn.part = true; kn.node_id_layout = !h->parts_vocab_order;
-    // Duty cycle.  The rule bounds the negative rows that are OPEN at any time (W x 5 x w of them).  A wavefront of a bucket launch spends only part of
-    // its time in pair steps: per walk it has walk_len x (window + 1) x 0.95 / parts^2 pairs to train but still 2 x walk_len / parts rows (the contexts and
-    // the centre words of its two partitions) to fetch and return, each an exposed round trip of ~0.7 pair steps.  With that fraction f of the time in
-    // pair steps the same bound on open rows allows W / f wavefronts (f = 0.88 for one partition -- left at 1, the validated rule --, 0.65 at 4, 0.47 at 8).
-    if (h->parts > 1) {
-        const double pairs_pp = (double)walk_len * (window + 1) * 0.95 / ((double)h->parts * h->parts), rows_pp = 2.0 * walk_len / h->parts;
-        kn.duty = pairs_pp / (pairs_pp + 0.7 * rows_pp);
-        // the pairs a bucket launch trains all have their context in ONE partition and their negatives in ONE partition: a row of those partitions is touched
-        // `parts` times as often per trained pair as in the whole corpus (sum over the partition's rows of (parts x load)^2 = parts x touch2), in the
-        // fraction `duty` of the time
-        kn.touch_scale = (double)h->parts * kn.duty;
-        // from ~4 partitions on a walk's contexts of one partition fit the window's slots and stay cached for the WHOLE walk (sgns_win_kernel<PART>,
-        // whole-walk mode): a node then sits in W x walk_len x count / tokens windows, which is what decides whether it is hot
-        if (walk_len / h->parts <= 2 * std::min(window, 10) + 1) kn.window_span = walk_len;
-    }
-    kn.has_local_hot = !(flags & 4) && h->hotkey_state == 2 && h->n_local_hot > 0;       // LOCALLY HOT ROWS of the gathered corpus (gemhip_n2v_locally_hot_corpus)
+    VocabStats vs;
+    const SgnsKnobs kn = bucket_knobs(h->kn, h->vs_part[word_part], h->vs, h->parts, walk_len, window, flags, !h->parts_vocab_order, h->hotkey_state == 2 && h->n_local_hot > 0, &vs);
     const SgnsLaunchPlan P = plan_sgns_launch(vs, kn, (int64_t)A.n, d, window, walk_len, nwalks, flags);
     GEMHIP_REQUIRE(P.window, "sgns_train_part: d=%d window=%d walk_len=%d do not fit the LDS window kernel", d, window, walk_len);
     A.nwaves = (int32_t)P.waves; A.cache_radius = P.R; A.hot_thr = P.hot_thr;
@@ -1426,21 +1143,6 @@ extern "C" int gemhip_test_wave_sum6(const float *in_host, float *out_host)
     return GEMHIP_OK;
 }
 
-extern "C" int gemhip_sgns_set_hogwild(gemhip_n2v_t h, int32_t prefetch_pairs, int32_t reload_on_update)
-{
-    GEMHIP_REQUIRE(h && prefetch_pairs >= 0 && prefetch_pairs <= 2 && reload_on_update >= -1 && reload_on_update <= 1, "sgns_set_hogwild: bad arguments");
-    if (prefetch_pairs) h->kn.prefetch = prefetch_pairs;
-    if (reload_on_update >= 0) h->kn.reload = reload_on_update;
-    return GEMHIP_OK;
-}
-
-extern "C" int gemhip_sgns_set_hot_rows(gemhip_n2v_t h, int32_t min_count)
-{
-    GEMHIP_REQUIRE(h && min_count >= -1, "sgns_set_hot_rows: bad arguments");
-    h->kn.hot_count = min_count;
-    return GEMHIP_OK;
-}
-
 // ... the same key from a walk CORPUS assembled from every rank's shard (the partitioned N-GPU schedule: gemhip_sgns_train_part trains buckets of it), with
 // the handle's -- all-reduced -- token counts: rows of -1 tokens (padding of shorter shards) count nothing.  Bucket launches on this handle then treat the
 // locally hot nodes as hot rows (hotkey is indexed by GLOBAL node id, like the counts the bucket kernels read).
@@ -1450,20 +1152,9 @@ extern "C" int gemhip_n2v_locally_hot_corpus(gemhip_n2v_t h, const void *d_corpu
     if (per_walk >= 0) h->kn.local_hot = per_walk;
     h->hotkey_state = 0; h->n_local_hot = 0;
     if (h->kn.local_hot == 0) { if (count) *count = 0; return GEMHIP_OK; }
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = ensure_hotkey_buffers(h)) return rc;
-    GEMHIP_CHECK(hipMemsetAsync(h->d_wcount, 0, (size_t)h->n * sizeof(int32_t), s));
-    GEMHIP_CHECK(hipMemsetAsync(h->d_nlocal, 0, sizeof(unsigned int), s));
-    hipLaunchKernelGGL(n2v_walk_presence_kernel, dim3((unsigned)std::min<int64_t>(corpus_rows, 256 * 32)), dim3(64), (size_t)walk_len * sizeof(int32_t), s, (const int32_t *)d_corpus,
-                       corpus_rows, walk_len, h->d_wcount);
-    hipLaunchKernelGGL(n2v_hotkey_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, s, h->n, h->d_counts, h->d_wcount, h->kn.local_hot, h->d_hotkey, h->d_nlocal);
-    GEMHIP_CHECK(hipGetLastError());
-    unsigned int nl = 0;
-    GEMHIP_CHECK(hipMemcpyAsync(&nl, h->d_nlocal, sizeof nl, hipMemcpyDeviceToHost, s));
-    GEMHIP_CHECK(hipStreamSynchronize(s));
-    h->n_local_hot = nl;
-    h->hotkey_state = 2;                 // built from a corpus: gemhip_sgns_train_part uses it; gemhip_sgns_train rebuilds its own from the handle's walks
-    if (count) *count = nl;
+    // (state 2: gemhip_sgns_train_part uses it; gemhip_sgns_train rebuilds its own from the handle's walks)
+    if (int rc = build_hotkey(h, (const int32_t *)d_corpus, corpus_rows, walk_len, (hipStream_t)stream, 2)) return rc;
+    if (count) *count = h->n_local_hot;
     return GEMHIP_OK;
 }
 
@@ -1483,21 +1174,22 @@ extern "C" int gemhip_n2v_locally_hot(gemhip_n2v_t h, int32_t per_walk, int64_t 
     return GEMHIP_OK;
 }
 
-extern "C" int gemhip_sgns_set_fresh(gemhip_n2v_t h, int32_t bits)
-{
-    GEMHIP_REQUIRE(h && bits >= 0 && bits <= 7, "sgns_set_fresh: bits=%d (0..7)", bits);
-    h->kn.fresh = bits;
-    return GEMHIP_OK;
-}
-
 extern "C" int gemhip_sgns_last_launch(gemhip_n2v_t h, int32_t *kernel, int32_t *waves, int32_t *hot_threshold, int32_t *fresh)
 {
     GEMHIP_REQUIRE(h, "sgns_last_launch: null handle");
     const SgnsLaunchPlan &P = h->last_plan;
-    if (kernel) *kernel = !P.window ? 0 : P.delta ? 2 : 1;
+    if (kernel) *kernel = P.kernel();
     if (waves) *waves = (int32_t)P.waves;
     if (hot_threshold) *hot_threshold = P.hot_thr;
     if (fresh) *fresh = h->last_fresh;
+    return GEMHIP_OK;
+}
+
+// ------------------------------------------------------------------ launch knobs (per handle; the environment overrides are read once, in gemhip_n2v_create)
+extern "C" int gemhip_n2v_set_max_waves(gemhip_n2v_t h, int32_t max_waves)
+{
+    GEMHIP_REQUIRE(h && max_waves >= 0, "n2v_set_max_waves: bad arguments");
+    h->kn.max_waves = max_waves;
     return GEMHIP_OK;
 }
 
@@ -1506,6 +1198,28 @@ extern "C" int gemhip_sgns_set_window_cache(gemhip_n2v_t h, int32_t radius, int3
     GEMHIP_REQUIRE(h && radius >= -1 && radius <= 31 && delta_writeback >= -1 && delta_writeback <= 1, "sgns_set_window_cache: bad arguments");
     h->kn.cache_radius = radius;
     h->kn.cache_delta = delta_writeback;
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_sgns_set_hogwild(gemhip_n2v_t h, int32_t prefetch_pairs, int32_t reload_on_update)
+{
+    GEMHIP_REQUIRE(h && prefetch_pairs >= 0 && prefetch_pairs <= 2 && reload_on_update >= -1 && reload_on_update <= 1, "sgns_set_hogwild: bad arguments");
+    if (prefetch_pairs) h->kn.prefetch = prefetch_pairs;
+    if (reload_on_update >= 0) h->kn.reload = reload_on_update;
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_sgns_set_hot_rows(gemhip_n2v_t h, int32_t min_count)
+{
+    GEMHIP_REQUIRE(h && min_count >= -1, "sgns_set_hot_rows: bad arguments");
+    h->kn.hot_count = min_count;
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_sgns_set_fresh(gemhip_n2v_t h, int32_t bits)
+{
+    GEMHIP_REQUIRE(h && bits >= 0 && bits <= 7, "sgns_set_fresh: bits=%d (0..7)", bits);
+    h->kn.fresh = bits;
     return GEMHIP_OK;
 }
 

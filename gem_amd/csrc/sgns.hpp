@@ -4,42 +4,46 @@
 //   sgns_det.hip      sgns_win_kernel<.., DELTA = false, ..> + sgns_kernel   deterministic / single-wavefront launches and d >= 384
 //   sgns_part.hip     sgns_win_kernel<.., PART = true>   one bucket (SynPos partition g x SynNeg partition h) of the partitioned N-GPU schedule
 //   n2v.hip           the C ABI (gemhip_sgns_train / gemhip_sgns_train_part pick a launcher), walks, alias tables
+//   sgns_plan.hip     no kernel: the host arithmetic (launch rule, unigram tables; sgns_plan.hpp also defines the constants and row sizes shared with it)
 // Every kernel template is instantiated in exactly one of them; the helpers below are inlined wherever they are used.
 #pragma once
 #include "common.hpp"
+#include "sgns_plan.hpp"
 #include <type_traits>
 #include <cstdint>
 
 namespace gemhip {
 
+static_assert(SGNS_WAVE == WAVE, "the launch rule (sgns_plan.hpp) sizes LDS for the wavefront the kernels run on");
+
 struct SgnsArgs {
-    const int32_t *walks; int64_t walk_lo, walk_hi; int32_t walk_len; int32_t window;
-    float alpha0; int64_t denom; int64_t token_offset; int64_t walk_id_offset; int32_t epoch;
+    const int32_t *walks = nullptr; int64_t walk_lo = 0, walk_hi = 0; int32_t walk_len = 0; int32_t window = 0;
+    float alpha0 = 0.f; int64_t denom = 0; int64_t token_offset = 0; int64_t walk_id_offset = 0; int32_t epoch = 0;
     // negative sampling (RndUnigramInt): slot = floor(u n) -> X = KT[slot] (flags & 2; else X = slot) -> target = u' < UK[X].x ? X : UK[X].y.  KT is indexed
     // by SLOT, UK = {UTable, KTable} by NODE: the same arrays in the node-id layout, different ones in the binary's vocabulary-order layout (n2v.hip)
-    const float *UT; const int32_t *KT; const uint2 *UK; uint32_t n; uint64_t seed; int32_t flags; int32_t d;
+    const float *UT = nullptr; const int32_t *KT = nullptr; const uint2 *UK = nullptr; uint32_t n = 0; uint64_t seed = 0; int32_t flags = 0; int32_t d = 0;
     // sgns_win_kernel: the same draw through ONE gather.  SK[slot] = {X, bits of UTable[X], KTable[X], 0} with X = KT[slot] (flags & 2) or slot: what the
     // two dependent gathers KT[slot] -> UK[X] return, laid out by slot (n2v.hip: n2v_slot_table_kernel, built once per table and quirk setting).  One
     // 16-byte random read per draw instead of a 4-byte and an 8-byte one: half the table sectors per pair (5 x 64 B less of ~6.5 KB, the counters
     // charge every sector) and one dependent round trip less in the negative-target pipeline
-    const uint4 *SK;
-    float *SynPos; float *SynNeg; int32_t nwaves; unsigned long long *pairs;
-    float *dummy;               // sgns_win_kernel: nwaves rows, never read for their value
-    unsigned long long *prof;   // GEMHIP_SGNS_PROFILE builds only: per-phase cycle sums (s_memtime)
-    int32_t cache_radius;       // sgns_win_kernel: tokens within this many positions of the centre keep their SynPos row in LDS
-    int32_t prefetch;           // sgns_win_kernel: pairs whose negative rows are requested ahead (2, or 1)
-    int32_t reload;             // sgns_win_kernel<RELOAD>: negative rows updated as they are at store time, centre row by atomic add
-    const int32_t *counts; int32_t hot_thr;   // sgns_win_kernel<!ALLC>: nodes with counts[v] >= hot_thr > 0 never enter the LDS window (HOT ROWS below); `counts` is the
+    const uint4 *SK = nullptr;
+    float *SynPos = nullptr; float *SynNeg = nullptr; int32_t nwaves = 1; unsigned long long *pairs = nullptr;
+    float *dummy = nullptr;              // sgns_win_kernel: nwaves rows, never read for their value
+    unsigned long long *prof = nullptr;   // GEMHIP_SGNS_PROFILE builds only: per-phase cycle sums (s_memtime)
+    int32_t cache_radius = 0;   // sgns_win_kernel: tokens within this many positions of the centre keep their SynPos row in LDS
+    int32_t prefetch = 2;       // sgns_win_kernel: pairs whose negative rows are requested ahead (2, or 1)
+    int32_t reload = 1;         // sgns_win_kernel<RELOAD>: negative rows updated as they are at store time, centre row by atomic add
+    const int32_t *counts = nullptr; int32_t hot_thr = 0;   // sgns_win_kernel<!ALLC>: nodes with counts[v] >= hot_thr > 0 never enter the LDS window (HOT ROWS below); `counts` is the
                                               // token count, or -- single-GPU Hogwild launches -- n2v.hip's hotkey: INT32_MAX for a LOCALLY hot node (tokens packed into few walks)
     // sgns_win_kernel<PART> (partitioned tables, N-GPU schedule): node v belongs to partition v % parts, local row v / parts.  SynPos / SynNeg point
     // at partition ctx_part of SynPos and partition word_part of SynNeg; UT / KT / UK / n describe the unigram table RESTRICTED to word_part (local
     // indices); `counts` stays global.  Only pairs (context in ctx_part, centre word in word_part) are trained: TrainModel filtered to one bucket.
-    int32_t parts, ctx_part, word_part;
+    int32_t parts = 0, ctx_part = 0, word_part = 0;
     // a corpus assembled from several ranks' walk shards: work item wl = r * seg_len + j is walk j of segment r, stored at row seg[r] + j of
     // `walks`, present when j < seg[nseg + r], with global walk id (the Philox key) seg[2 * nseg + r] + j.  seg == nullptr: one segment, row = wl,
     // walk id = walk_id_offset + wl
-    const int64_t *seg; int32_t nseg; int64_t seg_len;
-    float *scratch;             // sgns_win_kernel<PART, DELTA>: nwaves x (2R+1) rows -- the window rows as loaded (delta write-back), kept out of LDS
+    const int64_t *seg = nullptr; int32_t nseg = 0; int64_t seg_len = 0;
+    float *scratch = nullptr;   // sgns_win_kernel<PART, DELTA>: nwaves x (2R+1) rows -- the window rows as loaded (delta write-back), kept out of LDS
     // FRESH HOT ROWS (round 6; Hogwild launches that have hot rows).  bit 0: a hot centre word's positive row SynNeg[word] takes every pair's update as a
     // RETURNING atomic add -- the next pair computes with the row as memory held it one pair step ago (what came back + this pair's own change), not with
     // the copy loaded at the centre's start, ~10 pair steps old by the centre's end.  bit 1: hot negative rows are fetched AGAIN right before the dot
@@ -48,8 +52,8 @@ struct SgnsArgs {
     // unigram^0.75 draw -- under RndUnigramInt's quirk: over the alias targets only -- concentrates on a few thousand mid-frequency rows that are "cold" by
     // the window's measure (token count) but are touched by another wavefront inside one's load..store interval a third of the time at 768 wavefronts
     // (profiles/r06_staleness_rmat17.jsonl): the reload + store then overwrites that update.
-    int32_t fresh; int32_t neg_thr;
-    unsigned int *stale_ver; unsigned long long *stale_hist; int64_t n_nodes;   // GEMHIP_SGNS_STALENESS builds only (see STALE below)
+    int32_t fresh = 0; int32_t neg_thr = 0;
+    unsigned int *stale_ver = nullptr; unsigned long long *stale_hist = nullptr; int64_t n_nodes = 0;   // GEMHIP_SGNS_STALENESS builds only (see STALE below)
 };
 
 using sgns_fn = void (*)(const SgnsArgs &, int blocks, int threads, size_t lds, hipStream_t);
@@ -57,20 +61,13 @@ sgns_fn pick_sgns(int d);                    // sgns_det.hip: sgns_kernel (no LD
 sgns_fn pick_sgns_win_det(int d);            // sgns_det.hip: sgns_win_kernel, overwrite on leave (bit-compatible with sgns_kernel on one wavefront)
 sgns_fn pick_sgns_win_hogwild(int d);        // sgns_hogwild.hip: sgns_win_kernel, delta write-back
 sgns_fn pick_sgns_win_part(int d, bool hogwild);   // sgns_part.hip: sgns_win_kernel<PART> (one bucket of the partitioned schedule), Hogwild or single-wavefront
-// floats one cached row occupies in LDS and in the per-wave scratch row: RW = NV * VEC * 64 of the kernel the pickers INSTANTIATE for d
-// (NV is 1, 2 or 4: three chunks run on the NV = 4 kernel, so d = 129..191 odd and 258..384 even occupy 256 / 512 floats, not 192 / 384;
-// round 3 sized LDS and the scratch rows from the chunk count and the NV = 4 kernels wrote past both -- ADVICE r3)
-inline int sgns_win_nv(int d) { const int nv = d % 2 == 0 ? (d + 127) / 128 : (d + 63) / 64; return nv <= 1 ? 1 : nv <= 2 ? 2 : 4; }
-inline int sgns_win_row_floats(int d) { return sgns_win_nv(d) * (d % 2 == 0 ? 128 : 64); }
 }  // namespace gemhip
 
 using namespace gemhip;
 
 namespace {
 enum { TAG_WALK = 1, TAG_WIN = 2, TAG_NEG = 3, TAG_INIT = 4 };
-constexpr int SGNS_NEG = 5;             // SNAP: NegSamN = 5 (compile-time constant there too)
 constexpr float SGNS_MAX_EXP = 6.0f;    // SNAP: MaxExp
-constexpr int HOGWILD_ROWS_PER_WAVE = 128;
 
 __host__ __device__ __forceinline__ uint32_t mulhi_range(uint32_t r, uint32_t n) { return (uint32_t)(((uint64_t)r * n) >> 32); }
 

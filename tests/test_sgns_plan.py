@@ -1,4 +1,4 @@
-"""CPU tests of the SGNS launch rule (gemhip_sgns_plan_launch, gem_amd/csrc/n2v.hip::plan_sgns_launch): host arithmetic, no device.
+"""CPU tests of the SGNS launch rule (gemhip_sgns_plan_launch, gem_amd/csrc/sgns_plan.hip::plan_sgns_launch): host arithmetic, no device.
 
 The reference has nothing to compare with -- the SNAP binary runs one Hogwild thread per core (gem/embedding/node2vec.py:34-53 passes no thread
 count) -- so what is pinned here is the rule DESIGN.md 3.3 derives and the settings the GPU parity tests were measured at:
@@ -63,7 +63,7 @@ def touch2_hub(c):
     return max(0.0, touch2(c) - 40.0 / max(1, int(np.count_nonzero(c))))
 
 
-TOUCH_BOUND = 0.165          # (W - 1) x touch2_hub: n2v.hip plan_sgns_launch, the conservative extrapolation of round 5 ...
+TOUCH_BOUND = 0.165          # (W - 1) x touch2_hub: sgns_plan.hip plan_sgns_launch, the conservative extrapolation of round 5 ...
 TOUCH_FLOOR = 256            # ... which never takes a launch below 256 wavefronts (round 6: at 256 R-MAT scale 17 / 20 sit at -0.45 / -1.3 % of the oracle's MAP)
 
 
@@ -138,3 +138,77 @@ def test_bad_arguments():
     c = np.ones(4, dtype=np.int32)
     assert L.gemhip_sgns_plan_launch(_hip.ptr(c, C.c_int32), 4, 0, 10, 80, 1, 11, None, None, None, None, None) != 0
     assert L.gemhip_sgns_plan_launch(_hip.ptr(c, C.c_int32), 4, 16, 10, 80, 1, 11, None, None, None, None, None) == 0
+
+
+def test_stand_alone_driver_reproduces_the_recorded_grid_and_the_oracle_tables(tmp_path, sbm1024):
+    """gem_amd/csrc/sgns_plan.hip as plain C++ behind scripts/asan/plan_driver.cpp (no HIP, no library): the launch-rule grid -- every knob, bucket_knobs
+    for 1 / 2 / 4 / 8 partitions -- byte for byte as recorded before the rule moved out of n2v.hip (tests/golden/sgns_plan_grid.txt, CHANGELOG.md), the
+    invariants of the unified table builder on small inputs (the driver's exit status), and that builder's tables on the SBM-1024 corpus of the CPU
+    oracle against the oracle's four builders: the same integers, the same fp32 bits."""
+    import os
+    import subprocess
+    import oracle
+    from gem_amd import build
+    from gem_amd.graph import edge_arrays
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc_dir = os.path.dirname(os.path.realpath(build.HIPCC))
+    cxx = next(c for c in (os.path.join(hipcc_dir, '..', 'lib', 'llvm', 'bin', 'clang++'), os.path.join(hipcc_dir, 'clang++'), os.path.join(hipcc_dir, 'amdclang++'))
+               if os.path.exists(c))
+    exe = str(tmp_path / 'plan_driver')
+    subprocess.check_call([cxx, '-std=c++17', '-O2', '-Wall', '-Werror', '-x', 'c++', os.path.join(root, 'gem_amd', 'csrc', 'sgns_plan.hip'),
+                           os.path.join(root, 'scripts', 'asan', 'plan_driver.cpp'), '-o', exe])
+    golden = os.path.join(root, 'tests', 'golden')
+    run = subprocess.run([exe, 'grid', os.path.join(golden, 'rmat_token_count_histograms.json')], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert run.returncode == 0, run.stderr.decode()[-2000:]
+    assert run.stdout == open(os.path.join(golden, 'sgns_plan_grid.txt'), 'rb').read()
+
+    def tables(counts, order, parts, flags):
+        n = len(counts)
+        with open(tmp_path / 'in', 'wb') as f:
+            np.array([n, parts, flags, order is not None], np.int32).tofile(f)
+            np.ascontiguousarray(counts, np.int32).tofile(f)
+            if order is not None:
+                np.ascontiguousarray(order, np.int32).tofile(f)
+        subprocess.check_call([exe, 'tables', str(tmp_path / 'in'), str(tmp_path / 'out')])
+        with open(tmp_path / 'out', 'rb') as f:
+            rc = int(np.fromfile(f, np.int32, 1)[0]); n_vocab = int(np.fromfile(f, np.int64, 1)[0])
+            U = np.fromfile(f, np.float32, n); K = np.fromfile(f, np.int32, n); slot = np.fromfile(f, np.int32, n)
+            off = np.fromfile(f, np.int64, parts + 1); nslots = np.fromfile(f, np.int64, parts)
+        assert rc == -1
+        return n_vocab, U, K, slot, off, nslots
+
+    n, src, dst, w, _ = edge_arrays(sbm1024)
+    row_ptr, col, _ = oracle.sorted_csr(n, src, dst, w)
+    walks = oracle.n2v_walks(row_ptr, col, None, None, 1.0, 1.0, 2, 20, 5, 11)
+    walks[1::7, 10:] = -1                                         # padded tails, as the shorter shards of a gathered corpus have them
+    counts = oracle.n2v_vocab(n, walks)
+    gone = int(counts.argmax())                                   # ... and a node the corpus does not name (its tokens: padding)
+    walks[walks == gone] = -1
+    counts = oracle.n2v_vocab(n, walks)
+    assert np.flatnonzero(counts == 0).tolist() == [gone]
+    flat = walks.ravel()
+    first = np.full(n, flat.size, np.int64)
+    np.minimum.at(first, flat[flat >= 0], np.flatnonzero(flat >= 0))
+    order = np.argsort(first, kind='stable').astype(np.int32)     # first-appearance order, the node that never occurs last
+    bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)
+    for parts in (1, 2, 4):
+        # node-id layout: Vose over every row of a partition, in id order
+        n_vocab, U, K, slot, off, nslots = tables(counts, None, parts, 11)
+        UT, KT, ooff = oracle.unigram_build_parts(counts, parts)
+        assert list(off) == list(ooff) and n_vocab == n and list(nslots) == list(np.diff(ooff)) and np.all(slot == -1)
+        assert np.array_equal(bits(U), bits(UT)) and np.array_equal(K, KT)
+        if parts == 1:
+            UT1, KT1 = oracle.unigram_build(counts)
+            assert np.array_equal(bits(U), bits(UT1)) and np.array_equal(K, KT1)
+        # the binary's layout: the partition's nodes that occur, in first-appearance order; with and without RndUnigramInt's quirk in the slot table
+        for flags in (27, 25):
+            n_vocab, U, K, slot, off, nslots = tables(counts, order, parts, flags)
+            want = oracle.unigram_build_parts_vocab_order(counts, walks, parts, flags)
+            assert n_vocab == n - 1 == int(nslots.sum())
+            for p, (st, UTp, KTp) in enumerate(want):
+                a, b = int(off[p]), int(off[p + 1])
+                assert nslots[p] == len(st) and np.array_equal(slot[a:a + len(st)], st) and np.all(slot[a + len(st):b] == -1)
+                assert np.array_equal(bits(U[a:b]), bits(UTp)) and np.array_equal(K[a:b], KTp)
+            if parts == 1:
+                st1, UTn, KTn = oracle.unigram_build_vocab_order(counts, walks, flags)[:3]
+                assert np.array_equal(slot[:len(st1)], st1) and np.array_equal(bits(U), bits(UTn)) and np.array_equal(K, KTn)
