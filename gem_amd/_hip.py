@@ -94,6 +94,11 @@ _SIGS = {
                                            f32p, C.c_int32]),
     'gemhip_test_hope_randn': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_uint64, f32p]),
     'gemhip_eval_sampled_ap': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, f32p, i64p, i32p, C.c_int32, C.c_int64, i32p, f64p]),
+    'gemhip_eval_create': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, f32p, C.c_int32, i64p, i32p, C.POINTER(C.c_void_p)]),
+    'gemhip_eval_ap': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, i32p, f64p]),
+    'gemhip_eval_pairs': (C.c_int, [C.c_void_p, C.c_int64, i32p, i32p, f64p, C.POINTER(C.c_uint8)]),
+    'gemhip_eval_last_pairs_ms': (C.c_int, [C.c_void_p, f64p]),
+    'gemhip_eval_destroy': (C.c_int, [C.c_void_p]),
     'gemhip_n2v_train': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_uint64, C.c_int32, f32p, f64p]),
     'gemhip_n2v_create': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.POINTER(C.c_void_p)]),

@@ -15,8 +15,17 @@
 // compares the score of the row with "its" neighbours' scores -- O(n d) per chunk, exact, no n x n matrix.  The kernel
 // returns (score, rank_all - 1) per true neighbour; rank_hit is a sort of <= deg(i) numbers, done on the host.
 // score(i, j) = A_i . B_j : A = B = X for GF / node2vec (X_i . X_j), A = X[:, :k], B = X[:, k:] for HOPE (hope.py:43-44).
+// kind 1 (Laplacian Eigenmaps, LLE): score(i, j) = exp(-(sqrt(sum_k (x_ik - x_jk)^2))^2), the scalar get_edge_weight of lap.py:74 / lle.py:53 in fp64
+// (differences of the fp32 inputs are exact in fp64; sqrt, then square, then exp).  Ranks and ties are decided on the exp OUTPUT: where exp saturates,
+// distinct distances fall into one tie class and the node id decides, as in the reference -- the classes are those of the device's fp64 exp.
+//
+// The evaluator handle (gemhip_eval_create) keeps the embedding and the CSR of the true graph on the device for three consumers:
+//   gemhip_eval_ap     the AP kernel above for sampled nodes;
+//   gemhip_eval_pairs  score + "is (st -> ed) an edge" for an explicit pair list: the reference's pair-sampled MAP / precision curve
+//                      (evaluation_util.py:5-26) and, over the edge list, its weighted reconstruction error (evaluate_graph_reconstruction.py:38-42).
 #include "common.hpp"
 #include <algorithm>
+#include <climits>
 #include <vector>
 
 using namespace gemhip;
@@ -34,7 +43,23 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     return v;
 }
 
-template <int NV>     // lane l holds columns (c*64 + l), c < NV  (da <= 64*NV)
+template <int KIND>
+__device__ __forceinline__ double finish_score(double sum)      // sum: the fp64 dot (kind 0) or the fp64 squared distance (kind 1)
+{
+    if (KIND == 0) return sum;
+    const double r = sqrt(sum);                                  // lap.py:74  exp(-power(norm(x_i - x_j), 2))
+    return exp(-(r * r));
+}
+
+template <int KIND>
+__device__ __forceinline__ double term(float a, float b)
+{
+    if (KIND == 0) return (double)a * (double)b;
+    const double t = (double)a - (double)b;
+    return t * t;
+}
+
+template <int NV, int KIND>     // lane l holds columns (c*64 + l), c < NV  (da <= 64*NV)
 __global__ __launch_bounds__(EV_BLOCK) void eval_ap_kernel(int64_t n, int da, const float *__restrict__ A, const float *__restrict__ B, int ldb,
                                                            int undirected, const int32_t *__restrict__ chunk_node, const int64_t *__restrict__ chunk_off,
                                                            const int32_t *__restrict__ chunk_cnt, const int32_t *__restrict__ nb,
@@ -57,8 +82,8 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_ap_kernel(int64_t n, int da, co
         double part = 0.0;
         const float *bj = B + j * ldb;
 #pragma unroll
-        for (int c = 0; c < NV; ++c) { const int cc = c * WAVE + lane; if (cc < da) part += (double)a[c] * (double)bj[cc]; }
-        return wave_sum_f64(part);
+        for (int c = 0; c < NV; ++c) { const int cc = c * WAVE + lane; if (cc < da) part += term<KIND>(a[c], bj[cc]); }
+        return finish_score<KIND>(wave_sum_f64(part));
     };
     for (int k = wave; k < nnb; k += EV_BLOCK / WAVE) {
         const double s = score(t_nb[k]);
@@ -91,17 +116,126 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_ap_kernel(int64_t n, int da, co
     for (int k = threadIdx.x; k < nnb; k += EV_BLOCK) { s_out[off + k] = s_nb[k]; cnt_out[off + k] = cnt_nb[k]; }
 }
 
+// ---- pair scoring: a 16-lane group per (st, ed); one row of A and one of B are gathered per pair (2*4*d bytes), nothing is reused, so the kernel
+// is a pure row gather.  Four pairs per wavefront keep all 64 lanes busy at d <= 64 and four times as many rows in flight as a wavefront per pair.
+// VEC (ld % 4 == 0: every row starts on 16 bytes): lane s of the group loads the float4 at columns 4*(16c + s), c < NV; the tail float4 of a row
+// with da % 4 != 0 stays inside the row's ld and its surplus elements are masked.  Otherwise lane s reads columns 64c + 16k + s one by one.
+// Each lane sums its terms in column order in fp64, then the 16 partial sums are folded by a fixed butterfly: no atomics, the same bits every run.
+constexpr int EP_BLOCK = 256;
+constexpr int EP_GROUP = 16;
+constexpr int EP_MAX_BLOCKS = 256 * 16;         // 16 workgroups per CU; further pairs are taken by the grid-stride loop
+
+template <int KIND, bool VEC, int NV>           // da <= 64*NV
+__global__ __launch_bounds__(EP_BLOCK) void eval_pairs_kernel(int da, int ld, const float *__restrict__ A, const float *__restrict__ B,
+                                                              const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col, int64_t npairs,
+                                                              const int32_t *__restrict__ st, const int32_t *__restrict__ ed,
+                                                              double *__restrict__ score_out, uint8_t *__restrict__ hit_out)
+{
+    const int sub = threadIdx.x & (EP_GROUP - 1);
+    const int64_t ngroups = (int64_t)gridDim.x * (EP_BLOCK / EP_GROUP);
+    for (int64_t p = ((int64_t)blockIdx.x * EP_BLOCK + threadIdx.x) / EP_GROUP; p < npairs; p += ngroups) {      // uniform within a group
+        const int i = st[p], j = ed[p];
+        const float *a = A + (int64_t)i * ld, *b = B + (int64_t)j * ld;
+        double part = 0.0;
+        if (VEC) {
+            float4 va[NV], vb[NV];
+#pragma unroll
+            for (int c = 0; c < NV; ++c) {
+                const int cc = (c * EP_GROUP + sub) * 4;
+                va[c] = cc < da ? *reinterpret_cast<const float4 *>(a + cc) : make_float4(0.f, 0.f, 0.f, 0.f);
+                vb[c] = cc < da ? *reinterpret_cast<const float4 *>(b + cc) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int c = 0; c < NV; ++c) {
+                const int cc = (c * EP_GROUP + sub) * 4;
+                if (cc < da) part += term<KIND>(va[c].x, vb[c].x);
+                if (cc + 1 < da) part += term<KIND>(va[c].y, vb[c].y);
+                if (cc + 2 < da) part += term<KIND>(va[c].z, vb[c].z);
+                if (cc + 3 < da) part += term<KIND>(va[c].w, vb[c].w);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < NV; ++c) {
+                float sa[4], sb[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int cc = c * 64 + k * EP_GROUP + sub;
+                    sa[k] = cc < da ? a[cc] : 0.f; sb[k] = cc < da ? b[cc] : 0.f;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) if (c * 64 + k * EP_GROUP + sub < da) part += term<KIND>(sa[k], sb[k]);
+            }
+        }
+#pragma unroll
+        for (int o = EP_GROUP / 2; o >= 1; o >>= 1) part += __shfl_xor(part, o);       // partners stay inside the group, which is all active or all idle
+        if (sub == 0) {
+            score_out[p] = i == j ? 0.0 : finish_score<KIND>(part);                   // zero diagonal of get_reconstructed_adj
+            if (hit_out) {                                                             // true_digraph.has_edge(st, ed): directed, columns sorted
+                int64_t lo = row_ptr[i], hi = row_ptr[i + 1];
+                const int64_t end = hi;
+                while (lo < hi) { const int64_t mid = lo + ((hi - lo) >> 1); if (col[mid] < j) lo = mid + 1; else hi = mid; }
+                hit_out[p] = (lo < end && col[lo] == j) ? 1 : 0;
+            }
+        }
+    }
+}
+
 }  // namespace
 
-extern "C" int gemhip_eval_sampled_ap(int64_t n, int32_t da, int32_t ld, const float *A_host, const float *B_host, const int64_t *row_ptr,
-                                      const int32_t *col, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out)
+struct gemhip_eval {
+    int64_t n = 0, nnz = 0; int da = 0, ld = 0, kind = 0; bool cols_sorted = true; int dev = 0;
+    std::vector<int64_t> row_ptr; std::vector<int32_t> col;          // host copy: the AP call cuts the sampled nodes' rows into chunks
+    DevBuf<float> A, B; DevBuf<int64_t> d_row_ptr; DevBuf<int32_t> d_col;
+    DevBuf<int32_t> d_st, d_ed; DevBuf<double> d_score; DevBuf<uint8_t> d_hit;     // pair scratch, grow-only
+    double last_pairs_ms = 0.0;
+    const float *dB() const { return B ? B.get() : A.get(); }
+};
+
+extern "C" int gemhip_eval_create(int64_t n, int32_t da, int32_t ld, const float *A_host, const float *B_host, int32_t kind, const int64_t *row_ptr,
+                                  const int32_t *col, gemhip_eval_t *out)
 {
-    GEMHIP_REQUIRE(n >= 1 && da >= 1 && da <= 512 && ld >= da && A_host && row_ptr && nsample >= 0 && (nsample == 0 || (nodes && ap_out)),
-                   "eval_sampled_ap: bad arguments (da <= 512)");
-    if (nsample == 0) return GEMHIP_OK;
-    for (int64_t k = 0; k < nsample; ++k) GEMHIP_REQUIRE(nodes[k] >= 0 && nodes[k] < n, "eval_sampled_ap: node %d outside [0,%lld)", nodes[k], (long long)n);
+    GEMHIP_REQUIRE(out, "eval_create: out is null");
+    *out = nullptr;
+    GEMHIP_REQUIRE(n >= 1 && n <= INT32_MAX && da >= 1 && da <= 512 && ld >= da && A_host && row_ptr, "eval_create: bad arguments (1 <= da <= 512, ld >= da, n < 2^31)");
+    GEMHIP_REQUIRE(kind == 0 || kind == 1, "eval_create: kind %d is neither 0 (inner product) nor 1 (exp of minus squared distance)", kind);
+    GEMHIP_REQUIRE(kind == 0 || !B_host || B_host == A_host, "eval_create: kind 1 scores one embedding against itself (B must be NULL)");
+    GEMHIP_REQUIRE(row_ptr[0] == 0, "eval_create: row_ptr[0] is %lld, not 0", (long long)row_ptr[0]);
+    for (int64_t i = 0; i < n; ++i) GEMHIP_REQUIRE(row_ptr[i + 1] >= row_ptr[i], "eval_create: row_ptr decreases at row %lld", (long long)i);
     const int64_t nnz = row_ptr[n];
-    GEMHIP_REQUIRE(nnz == 0 || col, "eval_sampled_ap: col is null");
+    GEMHIP_REQUIRE(nnz == 0 || col, "eval_create: col is null");
+    bool sorted = true;
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
+            GEMHIP_REQUIRE(col[e] >= 0 && col[e] < n, "eval_create: column %d outside [0,%lld)", col[e], (long long)n);
+            if (e > row_ptr[i] && col[e] < col[e - 1]) sorted = false;
+        }
+    gemhip_eval *h = new gemhip_eval;
+    h->n = n; h->nnz = nnz; h->da = da; h->ld = ld; h->kind = kind; h->cols_sorted = sorted;
+    h->row_ptr.assign(row_ptr, row_ptr + n + 1);
+    if (nnz) h->col.assign(col, col + nnz);
+    hipError_t e = hipGetDevice(&h->dev);
+    if (e == hipSuccess) e = h->A.upload(A_host, (size_t)n * ld);
+    if (e == hipSuccess && B_host && B_host != A_host) e = h->B.upload(B_host, (size_t)n * ld);
+    if (e == hipSuccess) e = h->d_row_ptr.upload(row_ptr, (size_t)n + 1);
+    if (e == hipSuccess) e = h->d_col.upload(col, (size_t)nnz);
+    if (e != hipSuccess) { delete h; return fail(GEMHIP_E_HIP, "eval_create: %s", hipGetErrorString(e)); }
+    *out = h;
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_eval_destroy(gemhip_eval_t h)
+{
+    delete h;
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_eval_ap(gemhip_eval_t h, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out)
+{
+    GEMHIP_REQUIRE(h && nsample >= 0 && (nsample == 0 || (nodes && ap_out)), "eval_ap: bad arguments");
+    if (nsample == 0) return GEMHIP_OK;
+    const int64_t n = h->n;
+    const int64_t *row_ptr = h->row_ptr.data(); const int32_t *col = h->col.data();
+    for (int64_t k = 0; k < nsample; ++k) GEMHIP_REQUIRE(nodes[k] >= 0 && nodes[k] < n, "eval_ap: node %d outside [0,%lld)", nodes[k], (long long)n);
     // ---- candidate true neighbours of every sampled node (j != i, j > i when undirected, each once), cut into chunks
     std::vector<int32_t> nb, chunk_node, chunk_cnt; std::vector<int64_t> chunk_off, node_off(nsample + 1, 0);
     std::vector<int32_t> tmp;
@@ -110,7 +244,6 @@ extern "C" int gemhip_eval_sampled_ap(int64_t n, int32_t da, int32_t ld, const f
         tmp.clear();
         for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
             const int t = col[e];
-            GEMHIP_REQUIRE(t >= 0 && t < n, "eval_sampled_ap: column %d outside [0,%lld)", t, (long long)n);
             if (t == i || (undirected && t < i)) continue;
             tmp.push_back(t);
         }
@@ -126,19 +259,20 @@ extern "C" int gemhip_eval_sampled_ap(int64_t n, int32_t da, int32_t ld, const f
     const int64_t nchunk = (int64_t)chunk_node.size(), total = (int64_t)nb.size();
     std::vector<double> s_host(std::max<int64_t>(total, 1)); std::vector<int32_t> cnt_host(std::max<int64_t>(total, 1));
     if (nchunk > 0) {
-        DevBuf<float> bufA, bufB; DevBuf<int32_t> dnb, dcn, dcc, dcnt; DevBuf<int64_t> dco; DevBuf<double> ds;
-        GEMHIP_CHECK(bufA.upload(A_host, (size_t)n * ld));
-        if (B_host && B_host != A_host) GEMHIP_CHECK(bufB.upload(B_host, (size_t)n * ld));
-        const float *dA = bufA, *dB = bufB ? bufB.get() : bufA.get();
+        DevBuf<int32_t> dnb, dcn, dcc, dcnt; DevBuf<int64_t> dco; DevBuf<double> ds;
+        const float *dA = h->A, *dB = h->dB();
+        const int da = h->da, ld = h->ld;
         GEMHIP_CHECK(dnb.upload(nb.data(), total));
         GEMHIP_CHECK(dcn.upload(chunk_node.data(), nchunk));
         GEMHIP_CHECK(dcc.upload(chunk_cnt.data(), nchunk));
         GEMHIP_CHECK(dco.upload(chunk_off.data(), nchunk));
         GEMHIP_CHECK(ds.reserve(total)); GEMHIP_CHECK(dcnt.reserve(total));
         const int nv = (da + WAVE - 1) / WAVE;
-#define EV_LAUNCH(NV) hipLaunchKernelGGL((eval_ap_kernel<NV>), dim3((unsigned)nchunk), dim3(EV_BLOCK), 0, 0, n, (int)da, dA, dB, (int)ld, (int)undirected, \
-                                         dcn.get(), dco.get(), dcc.get(), dnb.get(), ds.get(), dcnt.get())
-        if (nv <= 1) EV_LAUNCH(1); else if (nv <= 2) EV_LAUNCH(2); else if (nv <= 4) EV_LAUNCH(4); else EV_LAUNCH(8);
+#define EV_LAUNCH(NV, KIND) hipLaunchKernelGGL((eval_ap_kernel<NV, KIND>), dim3((unsigned)nchunk), dim3(EV_BLOCK), 0, 0, n, da, dA, dB, ld, (int)undirected, \
+                                               dcn.get(), dco.get(), dcc.get(), dnb.get(), ds.get(), dcnt.get())
+#define EV_LAUNCH_NV(KIND) do { if (nv <= 1) EV_LAUNCH(1, KIND); else if (nv <= 2) EV_LAUNCH(2, KIND); else if (nv <= 4) EV_LAUNCH(4, KIND); else EV_LAUNCH(8, KIND); } while (0)
+        if (h->kind == 0) EV_LAUNCH_NV(0); else EV_LAUNCH_NV(1);
+#undef EV_LAUNCH_NV
 #undef EV_LAUNCH
         GEMHIP_CHECK(hipGetLastError());
         GEMHIP_CHECK(hipMemcpy(s_host.data(), ds, total * 8, hipMemcpyDeviceToHost));
@@ -156,4 +290,69 @@ extern "C" int gemhip_eval_sampled_ap(int64_t n, int32_t da, int32_t ld, const f
         ap_out[k] = ord.empty() ? 0.0 : sum / (double)ord.size();
     }
     return GEMHIP_OK;
+}
+
+extern "C" int gemhip_eval_pairs(gemhip_eval_t h, int64_t npairs, const int32_t *st, const int32_t *ed, double *score_out, uint8_t *hit_out)
+{
+    GEMHIP_REQUIRE(h && npairs >= 0 && (npairs == 0 || (st && ed && score_out)), "eval_pairs: bad arguments");
+    if (npairs == 0) return GEMHIP_OK;
+    GEMHIP_REQUIRE(!hit_out || h->cols_sorted, "eval_pairs: the edge lookup needs every CSR row's columns in ascending order");
+    for (int64_t p = 0; p < npairs; ++p) {
+        GEMHIP_REQUIRE(st[p] >= 0 && st[p] < h->n, "eval_pairs: st[%lld] = %d outside [0,%lld)", (long long)p, st[p], (long long)h->n);
+        GEMHIP_REQUIRE(ed[p] >= 0 && ed[p] < h->n, "eval_pairs: ed[%lld] = %d outside [0,%lld)", (long long)p, ed[p], (long long)h->n);
+    }
+    GEMHIP_CHECK(h->d_st.upload(st, npairs));
+    GEMHIP_CHECK(h->d_ed.upload(ed, npairs));
+    GEMHIP_CHECK(h->d_score.reserve(npairs));
+    if (hit_out) GEMHIP_CHECK(h->d_hit.reserve(npairs));
+    const int da = h->da, ld = h->ld;
+    const int nv = (da + 63) / 64;
+    const bool vec = ld % 4 == 0;
+    const unsigned blocks = (unsigned)std::min<int64_t>((npairs + EP_BLOCK / EP_GROUP - 1) / (EP_BLOCK / EP_GROUP), EP_MAX_BLOCKS);
+    uint8_t *dhit = hit_out ? h->d_hit.get() : nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    GEMHIP_CHECK(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(GEMHIP_E_HIP, "eval_pairs: hipEventCreate failed"); }
+    (void)hipEventRecord(e0, 0);
+#define EP_LAUNCH(KIND, VEC, NV) hipLaunchKernelGGL((eval_pairs_kernel<KIND, VEC, NV>), dim3(blocks), dim3(EP_BLOCK), 0, 0, da, ld, h->A.get(), h->dB(), \
+                                                    h->d_row_ptr.get(), h->d_col.get(), npairs, h->d_st.get(), h->d_ed.get(), h->d_score.get(), dhit)
+#define EP_LAUNCH_NV(KIND, VEC) do { if (nv <= 1) EP_LAUNCH(KIND, VEC, 1); else if (nv <= 2) EP_LAUNCH(KIND, VEC, 2); else if (nv <= 4) EP_LAUNCH(KIND, VEC, 4); else EP_LAUNCH(KIND, VEC, 8); } while (0)
+    if (h->kind == 0) { if (vec) EP_LAUNCH_NV(0, true); else EP_LAUNCH_NV(0, false); }
+    else              { if (vec) EP_LAUNCH_NV(1, true); else EP_LAUNCH_NV(1, false); }
+#undef EP_LAUNCH_NV
+#undef EP_LAUNCH
+    hipError_t e = hipGetLastError();
+    (void)hipEventRecord(e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    GEMHIP_CHECK(e);
+    h->last_pairs_ms = ms;
+    GEMHIP_CHECK(hipMemcpy(score_out, h->d_score, npairs * 8, hipMemcpyDeviceToHost));
+    if (hit_out) GEMHIP_CHECK(hipMemcpy(hit_out, h->d_hit, npairs, hipMemcpyDeviceToHost));
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_eval_last_pairs_ms(gemhip_eval_t h, double *ms_out)
+{
+    GEMHIP_REQUIRE(h && ms_out, "eval_last_pairs_ms: bad arguments");
+    *ms_out = h->last_pairs_ms;
+    return GEMHIP_OK;
+}
+
+// One-shot form of create + ap + destroy for inner-product scores (kind 0).
+extern "C" int gemhip_eval_sampled_ap(int64_t n, int32_t da, int32_t ld, const float *A_host, const float *B_host, const int64_t *row_ptr,
+                                      const int32_t *col, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out)
+{
+    GEMHIP_REQUIRE(n >= 1 && da >= 1 && da <= 512 && ld >= da && A_host && row_ptr && nsample >= 0 && (nsample == 0 || (nodes && ap_out)),
+                   "eval_sampled_ap: bad arguments (da <= 512)");
+    if (nsample == 0) return GEMHIP_OK;
+    for (int64_t k = 0; k < nsample; ++k) GEMHIP_REQUIRE(nodes[k] >= 0 && nodes[k] < n, "eval_sampled_ap: node %d outside [0,%lld)", nodes[k], (long long)n);
+    gemhip_eval_t h = nullptr;
+    int rc = gemhip_eval_create(n, da, ld, A_host, B_host, 0, row_ptr, col, &h);
+    if (rc != GEMHIP_OK) return rc;
+    rc = gemhip_eval_ap(h, undirected, nsample, nodes, ap_out);
+    gemhip_eval_destroy(h);
+    return rc;
 }

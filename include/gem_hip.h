@@ -519,6 +519,30 @@ int gemhip_eval_sampled_ap(int64_t n, int32_t da, int32_t ld, const float *A_hos
                            const int64_t *row_ptr, const int32_t *col, int32_t undirected,
                            int64_t nsample, const int32_t *nodes, double *ap_out);
 
+/* Evaluator handle: the embedding and the CSR of the TRUE graph are uploaded once and serve the three calls below, so that the
+ * reference's whole return tuple (MAP, precision curve, err, err_baseline of evaluate_graph_reconstruction.py:8-46) is available
+ * at sizes where the n x n matrix cannot be formed.
+ * kind 0: score(i, j) = A_i . B_j, as above (B_host NULL = A).
+ * kind 1: score(i, j) = exp(-(sqrt(sum_k (a_ik - a_jk)^2))^2) in fp64, B_host NULL: the scalar get_edge_weight of Laplacian Eigenmaps
+ *         and LLE (lap.py:74, lle.py:53) -- differences of the fp32 inputs are exact in fp64; sqrt, then square, then exp.  Ranks
+ *         and ties are decided on the exp output; where it saturates the tie classes are those of the device's fp64 exp, which may
+ *         differ from the host libm's by one ulp.
+ * A_host, B_host: [n][ld] float32, 1 <= da <= 512.  row_ptr/col are copied; gemhip_eval_pairs' edge lookup needs every row's
+ * columns in ascending order (duplicates allowed), gemhip_eval_ap does not. */
+typedef struct gemhip_eval *gemhip_eval_t;
+int gemhip_eval_create(int64_t n, int32_t da, int32_t ld, const float *A_host, const float *B_host, int32_t kind,
+                       const int64_t *row_ptr, const int32_t *col, gemhip_eval_t *out);
+/* gemhip_eval_sampled_ap's result for `nodes`, with the handle's score kind. */
+int gemhip_eval_ap(gemhip_eval_t h, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out);
+/* For every pair p: score_out[p] = (st == ed) ? 0 : score(st, ed)   (the zero diagonal of get_reconstructed_adj,
+ * static_graph_embedding.py:48-65), hit_out[p] = 1 if the CSR holds the arc st -> ed (true_digraph.has_edge; directed), else 0.
+ * hit_out may be NULL.  npairs = 0 is legal.  fp64 accumulation in a fixed order, no atomics: identical bits on every run. */
+int gemhip_eval_pairs(gemhip_eval_t h, int64_t npairs, const int32_t *st, const int32_t *ed, double *score_out,
+                      uint8_t *hit_out);
+/* Device time of the last gemhip_eval_pairs kernel of this handle, milliseconds (HIP events). */
+int gemhip_eval_last_pairs_ms(gemhip_eval_t h, double *ms_out);
+int gemhip_eval_destroy(gemhip_eval_t h);
+
 #ifdef __cplusplus
 }
 #endif
