@@ -59,6 +59,14 @@ struct gemhip_gf_plan {
     // Auto: 2 on the K-rows-per-wavefront kernel (the big levels), 0 on the one-row kernel (small, L2-resident levels, where nothing needs evicting).
     // A hint only: results are bit-identical either way.
     int nt_store = getenv("GEMHIP_GF_NT_STORE") ? atoi(getenv("GEMHIP_GF_NT_STORE")) : -1;
+    // Unit schedule (gemhip_gf_plan_create_any_order on a list the row schedule cannot represent).  The same arrays, read differently: d_rows holds one
+    // entry per UNIT (a run of one row's edges), row id | (1u<<31 if the unit loads its own row from X_new: the row was already written this sweep),
+    // d_ptr / d_col / d_w its edges in file order, level_off the units of each level; nrows counts units.  level_hubs / level_maxlen stay empty.
+    bool units = false;
+    int fused_levels = 0;             // gemhip_gf_plan_set_fused_levels: consecutive levels of at most this many units share one launch (0 = off)
+    DevBuf<int64_t> d_level_off;      // level_off on the device (gf_units_fused_kernel walks it)
+    struct seg { int l0, l1; bool fused; };
+    std::vector<seg> segs;            // the launches of one sweep: [l0, l1) is one level, or a fused run of small levels
 };
 
 namespace {
@@ -530,6 +538,173 @@ sweep_fn pick_sweep(int d)
     return nullptr;
 }
 
+// ---- unit schedule (any edge order; gemhip_gf_plan_create_any_order).  A UNIT is a run of one row's edges that one wavefront applies in file order:
+// it loads the row once -- from X_new when the row was already written in this sweep (bit 31 of its entry), else from X_old --, gathers every
+// neighbour from the table bit 31 of d_col names, and stores the row to X_new.  Units of one level touch no common row that one of them writes.
+// Same gf_apply_edge / gf_chunk as the row kernels: per edge the arithmetic is theirs bit for bit.  A unit of any length runs here (no hub path).
+template <int VEC, int NV>
+__device__ __forceinline__ void gf_unit_body(const uint32_t *__restrict__ units, const int64_t *__restrict__ ptr, const uint32_t *__restrict__ col,
+                                             const float *__restrict__ w, const float *Xold, float *Xnew, int64_t u, int d, int lane, float eta,
+                                             float regu)
+{
+    const uint32_t ru = units[u];
+    const int64_t i = (int64_t)(ru & 0x7fffffffu);
+    const int64_t e0 = ptr[u], e1 = ptr[u + 1];
+    float xi[NV][VEC];
+    const float *pi = ((ru >> 31) ? Xnew : Xold) + i * d;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) load_row<VEC>(pi, d, lane, c, xi[c]);
+    constexpr int DEEP = (GF_PREFETCH_DEEP / NV) >= GF_PREFETCH ? (GF_PREFETCH_DEEP / NV) : GF_PREFETCH;
+    for (int64_t e = e0; e < e1; e += WAVE) {
+        const int cnt = (int)((e1 - e) < (int64_t)WAVE ? (e1 - e) : (int64_t)WAVE);
+        const uint32_t cj = lane < cnt ? col[e + lane] : 0u;
+        const float wj = lane < cnt ? w[e + lane] : 0.f;
+        if (cnt == WAVE) gf_chunk<VEC, NV, DEEP>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
+        else gf_chunk<VEC, NV, GF_PREFETCH>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
+    }
+    store_row<VEC, NV>(Xnew + i * d, d, lane, xi, 0);
+}
+
+// The units [unit0, unit0 + nunits) of ONE level, one wavefront each.
+template <int VEC, int NV>
+__global__ __launch_bounds__(GF_BLOCK) void gf_sweep_units_kernel(const uint32_t *__restrict__ units, const int64_t *__restrict__ ptr,
+                                                                  const uint32_t *__restrict__ col, const float *__restrict__ w,
+                                                                  const float *Xold, float *Xnew, int64_t unit0, int64_t nunits, int d,
+                                                                  float eta, float regu)
+{
+    const int64_t slot = xcd_contiguous_block(blockIdx.x, gridDim.x) * GF_WAVES + (threadIdx.x >> 6);
+    if (slot >= nunits) return;
+    gf_unit_body<VEC, NV>(units, ptr, col, w, Xold, Xnew, unit0 + slot, d, lane_id(), eta, regu);
+}
+
+// The consecutive levels [l0, l1), each of at most GF_FUSED_WAVES units, in ONE launch of ONE workgroup: wavefront k runs unit k of the level, a
+// workgroup barrier stands where the level loop has a kernel boundary.  The workgroup's wavefronts share one CU and its vector L1, so the barrier (with
+// the workgroup-scope release / acquire __syncthreads carries: every store has left the wavefront before anyone passes) is all the ordering the rows
+// handed from level to level need.  Every wavefront executes every barrier: l0, l1 are kernel arguments, and the test `k < units of the level`
+// guards the unit body only.  Interleaving that comes from appended or concatenated files gives dozens of such levels in a row.
+constexpr int GF_FUSED_WAVES = 16;
+template <int VEC, int NV>
+__global__ __launch_bounds__(GF_FUSED_WAVES * WAVE) void gf_units_fused_kernel(const uint32_t *__restrict__ units, const int64_t *__restrict__ ptr,
+                                                                               const uint32_t *__restrict__ col, const float *__restrict__ w,
+                                                                               const int64_t *__restrict__ level_off, const float *Xold, float *Xnew,
+                                                                               int l0, int l1, int d, float eta, float regu)
+{
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    for (int l = l0; l < l1; ++l) {
+        const int64_t u0 = level_off[l], nu = level_off[l + 1] - u0;
+        if (wave < nu) gf_unit_body<VEC, NV>(units, ptr, col, w, Xold, Xnew, u0 + wave, d, lane, eta, regu);
+        __syncthreads();
+    }
+}
+
+template <int VEC, int NV>
+void launch_units(const gemhip_gf_plan *p, int64_t unit0, int64_t nunits, const float *Xold, float *Xnew, float eta, float regu, hipStream_t s)
+{
+    const int64_t blocks = (nunits + GF_WAVES - 1) / GF_WAVES;
+    const int64_t grid = (blocks + NUM_XCD - 1) / NUM_XCD * NUM_XCD;           // a multiple of 8: the XCD-contiguous map covers every slot
+    const int32_t *units = p->d_rows;
+    hipLaunchKernelGGL((gf_sweep_units_kernel<VEC, NV>), dim3((unsigned)grid), dim3(GF_BLOCK), 0, s, (const uint32_t *)units, p->d_ptr, p->d_col,
+                       p->d_w, Xold, Xnew, unit0, nunits, (int)p->d, eta, regu);
+}
+template <int VEC, int NV>
+void launch_units_fused(const gemhip_gf_plan *p, int l0, int l1, const float *Xold, float *Xnew, float eta, float regu, hipStream_t s)
+{
+    const int32_t *units = p->d_rows;
+    hipLaunchKernelGGL((gf_units_fused_kernel<VEC, NV>), dim3(1), dim3(GF_FUSED_WAVES * WAVE), 0, s, (const uint32_t *)units, p->d_ptr, p->d_col,
+                       p->d_w, p->d_level_off, Xold, Xnew, l0, l1, (int)p->d, eta, regu);
+}
+struct units_fns {
+    void (*level)(const gemhip_gf_plan *, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
+    void (*fused)(const gemhip_gf_plan *, int, int, const float *, float *, float, float, hipStream_t);
+};
+template <int VEC, int NV> units_fns units_of() { return {launch_units<VEC, NV>, launch_units_fused<VEC, NV>}; }
+units_fns pick_units(int d)      // the instantiations of pick_sweep
+{
+    if (d % 2 == 0) {
+        const int nv = (d + 127) / 128;
+        return nv <= 1 ? units_of<2, 1>() : nv <= 2 ? units_of<2, 2>() : nv <= 4 ? units_of<2, 4>() : units_of<2, 8>();
+    }
+    const int nv = (d + 63) / 64;
+    return nv <= 1 ? units_of<1, 1>() : nv <= 2 ? units_of<1, 2>() : nv <= 4 ? units_of<1, 4>() : units_of<1, 8>();
+}
+
+// the launches of one sweep of a unit plan: every maximal run of two or more consecutive levels of at most fused_levels units is one launch
+// (gf_units_fused_kernel), every other level one (gf_sweep_units_kernel)
+void gf_units_segments(gemhip_gf_plan *p)
+{
+    p->segs.clear();
+    const int nlevels = (int)p->level_off.size() - 1;
+    auto small = [&](int l) { return p->fused_levels > 0 && p->level_off[l + 1] - p->level_off[l] <= p->fused_levels; };
+    for (int l = 0; l < nlevels;) {
+        int e = l + 1;
+        if (small(l)) while (e < nlevels && small(e)) ++e;
+        p->segs.push_back({l, e, e - l > 1});
+        l = e;
+    }
+}
+
+// The any-order rule.  Walk the firing edges in file order; per row r: lastW[r] = level of the last unit that wrote r in this sweep (-1: not written
+// yet, the row is read from X_old), lastR[r] = highest level of a read of the CURRENT X_new version of r (-1 after every write of r; reads of X_old
+// never count: X_old is not written during the sweep), lastU[r] = r's latest unit.  Edge (i, j) must run after j's last write when it reads X_new[j]
+// (read after write) and after every read of i's current intermediate version (write after read): c is the higher of the two.  It joins i's latest
+// unit when that unit already runs after c, else it opens a unit one level above c and above i's last write.  Two firing edges that touch a common row
+// which one of them writes therefore sit in strictly ordered levels, or in one unit in file order: the result equals the sequential loop.  O(n + m).
+struct gf_unit_schedule {
+    std::vector<int32_t> unit_of;         // per edge: its unit (creation order), -1 = does not fire
+    std::vector<uint8_t> nb_new;          // per edge: the neighbour is read from X_new
+    std::vector<int32_t> row, level;      // per unit
+    std::vector<uint8_t> own_new;         // per unit: its own row is loaded from X_new
+    int32_t nlevels = 0;
+    int64_t nupd = 0;
+};
+int gf_schedule_units(const char *who, int64_t n, int64_t m, const int32_t *src, const int32_t *dst, gf_unit_schedule &S)
+{
+    std::vector<int32_t> lastW(n, -1), lastR(n, -1), lastU(n, -1);
+    S.unit_of.assign(m, -1); S.nb_new.assign(m, 0);
+    for (int64_t e = 0; e < m; ++e) {
+        const int32_t i = src[e], j = dst[e];
+        GEMHIP_REQUIRE(i >= 0 && i < n && j >= 0 && j < n, "%s: edge %lld = (%d,%d) outside [0,%lld)", who, (long long)e, i, j, (long long)n);
+        if (j <= i) continue;                        // does not fire (gf.py:95, gf.cpp:157)
+        GEMHIP_REQUIRE(S.row.size() < (size_t)0x7fffffff, "%s: more than 2^31 - 1 units", who);
+        const bool jn = lastW[j] >= 0;
+        const int32_t c = std::max(lastW[j], lastR[i]);
+        int32_t lv, u;
+        if (lastW[i] >= 0 && c < lastW[i]) { u = lastU[i]; lv = lastW[i]; }
+        else {
+            lv = std::max(c, lastW[i]) + 1;
+            u = (int32_t)S.row.size();
+            S.row.push_back(i); S.level.push_back(lv); S.own_new.push_back(lastW[i] >= 0);
+            lastU[i] = u;
+            S.nlevels = std::max(S.nlevels, lv + 1);
+        }
+        S.unit_of[e] = u; S.nb_new[e] = jn; ++S.nupd;
+        if (jn) lastR[j] = std::max(lastR[j], lv);
+        lastW[i] = lv; lastR[i] = -1;
+    }
+    return GEMHIP_OK;
+}
+
+// true when gemhip_gf_plan_create accepts the list: every firing edge reads a row that has had all or none of its updates of the sweep (the test of
+// gemhip_gf_plan_create, which also words the refusal).  A list with an endpoint out of range counts as accepted: that call reports it.
+bool gf_rows_schedule_represents(int64_t n, int64_t m, const int32_t *src, const int32_t *dst)
+{
+    std::vector<int64_t> first_t(n, -1), last_t(n, -1);
+    for (int64_t e = 0; e < m; ++e) {
+        const int32_t i = src[e], j = dst[e];
+        if (i < 0 || i >= n || j < 0 || j >= n) return true;
+        if (j <= i) continue;
+        if (first_t[i] < 0) first_t[i] = e;
+        last_t[i] = e;
+    }
+    for (int64_t e = 0; e < m; ++e) {
+        const int32_t i = src[e], j = dst[e];
+        if (j <= i || first_t[j] < 0) continue;
+        if (!(first_t[j] < first_t[i] ? last_t[j] < e : first_t[j] > e)) return false;
+    }
+    return true;
+}
+
 // 0.01*N(0,1)-style init: thread t fills elements 4t..4t+3 from one Philox block.
 __global__ void gf_init_kernel(float *X, int64_t total, uint64_t seed, float scale)
 {
@@ -707,6 +882,96 @@ extern "C" int gemhip_gf_plan_create(int64_t n, int64_t m, const int32_t *src, c
     return GEMHIP_OK;
 }
 
+extern "C" int gemhip_gf_any_order_schedule(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, int32_t *unit_out, int32_t *level_out,
+                                            int32_t *flags_out, int64_t *counts)
+{
+    GEMHIP_REQUIRE(n > 0 && n < (int64_t)0x7fffffff, "gf_any_order_schedule: n=%lld out of range", (long long)n);
+    GEMHIP_REQUIRE(m >= 0 && (m == 0 || (src && dst)), "gf_any_order_schedule: bad edge arrays");
+    gf_unit_schedule S;
+    if (int rc = gf_schedule_units("gf_any_order_schedule", n, m, src, dst, S)) return rc;
+    for (int64_t e = 0; e < m; ++e) {
+        const int32_t u = S.unit_of[e];
+        if (unit_out) unit_out[e] = u;
+        if (level_out) level_out[e] = u < 0 ? -1 : S.level[u];
+        if (flags_out) flags_out[e] = u < 0 ? -1 : (int32_t)S.nb_new[e] | ((int32_t)S.own_new[u] << 1);
+    }
+    if (counts) { counts[0] = (int64_t)S.row.size(); counts[1] = S.nlevels; }
+    return GEMHIP_OK;
+}
+
+constexpr int GF_FUSED_LEVELS_DEFAULT = 16;
+
+extern "C" int gemhip_gf_plan_create_any_order(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, const float *w, int32_t d,
+                                               int32_t flags, gemhip_gf_plan_t *out)
+{
+    GEMHIP_REQUIRE(out != nullptr, "gf_plan_create_any_order: out is NULL");
+    *out = nullptr;
+    GEMHIP_REQUIRE(n > 0 && n < (int64_t)0x7fffffff, "gf_plan_create_any_order: n=%lld out of range", (long long)n);
+    GEMHIP_REQUIRE(m >= 0 && (m == 0 || (src && dst)), "gf_plan_create_any_order: bad edge arrays");
+    GEMHIP_REQUIRE(d >= 1 && pick_sweep(d) != nullptr, "gf_plan_create_any_order: d=%d unsupported (even d <= 1024, odd d <= 512)", d);
+    GEMHIP_REQUIRE((flags & ~1) == 0, "gf_plan_create_any_order: flags=%d (bit 0 = force the unit schedule)", flags);
+    // a list the row schedule represents gets exactly that plan: same levels, same kernels, same speed
+    if (!(flags & 1) && gf_rows_schedule_represents(n, m, src, dst)) return gemhip_gf_plan_create(n, m, src, dst, w, d, 0, n, out);
+
+    const double t_host0 = phase_now();
+    gf_unit_schedule S;
+    if (int rc = gf_schedule_units("gf_plan_create_any_order", n, m, src, dst, S)) return rc;
+    // units sorted by level (inside a level: creation order), each unit's edges in file order
+    const int64_t nunits = (int64_t)S.row.size();
+    std::vector<int64_t> level_off(S.nlevels + 1, 0);
+    for (int64_t u = 0; u < nunits; ++u) ++level_off[S.level[u] + 1];
+    for (int32_t l = 0; l < S.nlevels; ++l) level_off[l + 1] += level_off[l];
+    std::vector<int64_t> slot(nunits), ptr(nunits + 1, 0);
+    std::vector<int32_t> units(nunits);
+    {
+        std::vector<int64_t> at(level_off.begin(), level_off.end() - 1);
+        for (int64_t u = 0; u < nunits; ++u) {
+            slot[u] = at[S.level[u]]++;
+            units[slot[u]] = (int32_t)((uint32_t)S.row[u] | (S.own_new[u] ? 0x80000000u : 0u));
+        }
+    }
+    for (int64_t e = 0; e < m; ++e) if (S.unit_of[e] >= 0) ++ptr[slot[S.unit_of[e]] + 1];
+    for (int64_t u = 0; u < nunits; ++u) ptr[u + 1] += ptr[u];
+    std::vector<uint32_t> col(S.nupd);
+    std::vector<float> wt(S.nupd);
+    {
+        std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
+        for (int64_t e = 0; e < m; ++e) {
+            if (S.unit_of[e] < 0) continue;
+            const int64_t q = fill[slot[S.unit_of[e]]]++;
+            col[q] = (uint32_t)dst[e] | (S.nb_new[e] ? 0x80000000u : 0u);
+            wt[q] = w ? w[e] : 1.0f;
+        }
+    }
+    auto *p = new gemhip_gf_plan();
+    p->n = n; p->d = d; p->nrows = nunits; p->nupd = S.nupd; p->units = true;
+    p->level_off = level_off;
+    p->fused_levels = GF_FUSED_LEVELS_DEFAULT;
+    gf_units_segments(p);
+    if (hipGetDevice(&p->device) != hipSuccess) { delete p; return fail(GEMHIP_E_HIP, "gf_plan_create_any_order: no HIP device"); }
+    phase_acc()[PH_HOST] += phase_now() - t_host0;
+    PhaseScope ph_up(PH_H2D);
+    hipError_t e = p->d_rows.upload(units.data(), nunits);
+    if (e == hipSuccess) e = p->d_ptr.upload(ptr.data(), nunits + 1);
+    if (e == hipSuccess) e = p->d_col.upload(col.data(), S.nupd);
+    if (e == hipSuccess) e = p->d_w.upload(wt.data(), S.nupd);
+    if (e == hipSuccess) e = p->d_level_off.upload(level_off.data(), level_off.size());
+    if (e != hipSuccess) {
+        gemhip_gf_plan_destroy(p);
+        return fail(GEMHIP_E_HIP, "gf_plan_create_any_order: device upload failed: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_gf_plan_set_fused_levels(gemhip_gf_plan_t p, int32_t max_units)
+{
+    GEMHIP_REQUIRE(p && max_units >= 0 && max_units <= GF_FUSED_WAVES, "gf_plan_set_fused_levels: 0 (off) .. %d units", GF_FUSED_WAVES);
+    p->fused_levels = max_units;
+    if (p->units) gf_units_segments(p);
+    return GEMHIP_OK;
+}
+
 extern "C" int gemhip_gf_plan_destroy(gemhip_gf_plan_t p)
 {
     if (!p) return GEMHIP_OK;
@@ -761,8 +1026,22 @@ extern "C" int gemhip_gf_plan_sweeps(gemhip_gf_plan_t p, int32_t nsweeps, float 
     GEMHIP_REQUIRE(p && nsweeps >= 0, "gf_plan_sweeps: bad arguments");
     GEMHIP_REQUIRE(p->X[0] && p->X[1], "gf_plan_sweeps: no embedding table (call set/init/bind first)");
     if (p->nrows == 0) return GEMHIP_OK;
-    const sweep_fn fn = pick_sweep((int)p->d);
     hipStream_t s = (hipStream_t)stream;
+    if (p->units) {                                    // unit schedule: the launches of gf_units_segments, in stream order
+        const units_fns uf = pick_units((int)p->d);
+        for (int it = 0; it < nsweeps; ++it) {
+            const float *Xold = p->X[p->cur];
+            float *Xnew = p->X[p->cur ^ 1];
+            for (const auto &g : p->segs) {
+                if (g.fused) uf.fused(p, g.l0, g.l1, Xold, Xnew, eta, regu, s);
+                else uf.level(p, p->level_off[g.l0], p->level_off[g.l1] - p->level_off[g.l0], Xold, Xnew, eta, regu, s);
+            }
+            p->cur ^= 1;
+        }
+        GEMHIP_CHECK(hipGetLastError());
+        return GEMHIP_OK;
+    }
+    const sweep_fn fn = pick_sweep((int)p->d);
     const int nlevels = (int)p->level_off.size() - 1;
     int it0 = 0;
     if (p->fused_sweeps > 1 && nlevels == 1 && (p->level_hubs.empty() || p->level_hubs[0] == 0) && pick_coop((int)p->d)) {
@@ -842,9 +1121,9 @@ extern "C" int gemhip_gf_plan_info(gemhip_gf_plan_t p, int64_t *info)
         int64_t bigmax = 0;
         for (size_t l = 0; l + 1 < p->level_off.size(); ++l)
             if (p->level_off[l + 1] - p->level_off[l] == big) bigmax = p->level_maxlen.size() > l ? p->level_maxlen[l] : 0;
-        info[6] = p->rows_per_wave > 0 ? p->rows_per_wave : (bigmax > 2 * WAVE ? 1 : gf_rows_per_wave(big));
+        info[6] = p->units ? 1 : p->rows_per_wave > 0 ? p->rows_per_wave : (bigmax > 2 * WAVE ? 1 : gf_rows_per_wave(big));
     }
-    info[7] = 0;
+    info[7] = p->units ? 1 : 0;
     return GEMHIP_OK;
 }
 

@@ -24,12 +24,19 @@ also kept in `self._objective_log`.
 devices through gemhip_gf_train_multi, or one process per GPU under torch.distributed -- with an all-gather of the owned row blocks after every sweep:
 the same table as one GPU, bit for bit.
 
-Edge order.  The sweep kernel reproduces the reference's Gauss-Seidel order exactly with two table copies, which needs every
-row a firing edge READS to have had all or none of its own updates of that sweep at that point of the edge list.  That holds for
-graph.edges() of any networkx graph and for saveGraphToEdgeListTxt files (edges grouped by source) -- every call site of the
-reference -- but not for arbitrary interleaved edge lists, which gf.cpp accepts: libgem_hip.so then returns GEMHIP_E_INVALID
-(raised here as GemHipError) instead of training something else.  `regroup_edges=True` opts into regrouping such a list by source
-(first-appearance order; gem_amd.graph.group_edges_by_source) -- a different visiting order than the reference's for that file.
+Edge order.  The default sweep kernel (one wavefront per source row) reproduces the reference's Gauss-Seidel order exactly with two
+table copies, which needs every row a firing edge READS to have had all or none of its own updates of that sweep at that point of the
+edge list.  That holds for graph.edges() of any networkx graph and for saveGraphToEdgeListTxt files (edges grouped by source) -- every
+call site of the reference -- but not for arbitrary interleaved edge lists (a shuffled file, two sorted files concatenated, edges
+appended later), which gf.cpp accepts.  By default libgem_hip.so then returns GEMHIP_E_INVALID (raised here as GemHipError) instead of
+training something else.  Two opt-ins:
+  * `exact_edge_order=True` trains graph.edges() / the EdgeListGraph arrays in exactly their order, whatever it is
+    (gemhip_gf_plan_create_any_order): a list the row schedule represents gets the very same plan as without the kwarg; any other list
+    gets the unit schedule (runs of one row's edges placed in dependency levels, DESIGN.md "GF: any edge order") -- the reference's
+    result, at more launches per sweep.  `self._stats` records 'schedule' ('rows' or 'units'), 'levels' and 'units'.  A unit schedule
+    is a single-device schedule: with n_gpus > 1 a list that needs it raises ValueError before any device call.
+  * `regroup_edges=True` regroups the list by source (first-appearance order; gem_amd.graph.group_edges_by_source) -- fast, but a
+    different visiting order than the reference's for that file.
 """
 import ctypes as C
 
@@ -58,6 +65,13 @@ class GraphFactorization(StaticGraphEmbedding):
         if getattr(self, '_regroup_edges', False):
             from gem_amd.graph import group_edges_by_source
             src, dst, w = group_edges_by_source(src, dst, w)
+        exact = bool(getattr(self, '_exact_edge_order', False))
+        if exact:
+            from gem_amd.embedding import _multi
+            from gem_amd.graph import row_schedule_represents
+            if _multi.resolve(self)[0] != 'single' and not row_schedule_represents(src, dst):
+                raise ValueError('exact_edge_order=True: this edge order needs the unit schedule, which is a single-device schedule; '
+                                 'n_gpus=%r (train on one GPU, or regroup_edges=True if the reordering is acceptable)' % (getattr(self, '_n_gpus', 1),))
         t_ingested = time.perf_counter()
         d = int(self._d)
         self._node_num = n
@@ -87,13 +101,17 @@ class GraphFactorization(StaticGraphEmbedding):
         device_init = getattr(self, '_device_init', None)
         if device_init is None:
             device_init = seed is not None
-        if device_init or verbose:
+        if device_init or verbose or exact:
             X0 = np.empty((n, d), dtype=np.float32)
             plan = C.c_void_p()
             info = (C.c_int64 * 8)()
             wf = _hip.as_f32(w)
-            _hip.check(L.gemhip_gf_plan_create(n, len(src), _hip.ptr(src, C.c_int32), _hip.ptr(dst, C.c_int32),
-                                               _hip.ptr(wf, C.c_float), d, 0, n, C.byref(plan)))
+            if exact:
+                _hip.check(L.gemhip_gf_plan_create_any_order(n, len(src), _hip.ptr(src, C.c_int32), _hip.ptr(dst, C.c_int32),
+                                                             _hip.ptr(wf, C.c_float), d, 0, C.byref(plan)))
+            else:
+                _hip.check(L.gemhip_gf_plan_create(n, len(src), _hip.ptr(src, C.c_int32), _hip.ptr(dst, C.c_int32),
+                                                   _hip.ptr(wf, C.c_float), d, 0, n, C.byref(plan)))
             t_plan = time.perf_counter()
             try:
                 if device_init:
@@ -130,6 +148,8 @@ class GraphFactorization(StaticGraphEmbedding):
                 L.gemhip_gf_plan_destroy(plan)
             t_called = time.perf_counter()
             self._stats = {'kernel_seconds': el, 'updates_per_sweep': info[0], 'rows_per_sweep': info[1], 'levels': info[2]}
+            if exact:
+                self._stats.update({'schedule': 'units' if info[7] else 'rows', 'units': info[1]})
             self._X = X0.astype(np.float64)
             t_end = time.perf_counter()
             # the breakdown of _hip.api_wall, stamped here: the staged calls are not one-shot drop-ins, gemhip_last_call_phases does not cover them

@@ -204,3 +204,21 @@ def group_edges_by_source(src, dst, w=None):
     np.minimum.at(first, src, np.arange(len(src)))
     order = np.argsort(first[src], kind='stable')
     return src[order], np.asarray(dst)[order], (None if w is None else np.asarray(w)[order])
+
+
+def row_schedule_represents(src, dst):
+    """True when GF's row schedule (one wavefront per source row, two table copies: gemhip_gf_plan_create) can reproduce the sequential loop
+    over this edge order: every firing edge (dst > src) reads a row that has had all or none of its own updates of the sweep at that point
+    of the list.  The test of gem_amd/csrc/gf.hip restated on arrays -- pure host code, so a caller can decide before any device call."""
+    src = np.asarray(src, dtype=np.int64); dst = np.asarray(dst, dtype=np.int64)
+    e = np.flatnonzero(dst > src)
+    if e.size == 0:
+        return True
+    i, j = src[e], dst[e]
+    n = int(j.max()) + 1
+    first = np.full(n, np.iinfo(np.int64).max, np.int64); last = np.full(n, -1, np.int64)
+    np.minimum.at(first, i, e)
+    np.maximum.at(last, i, e)
+    fires = last[j] >= 0
+    ok = np.where(first[j] < first[i], last[j] < e, first[j] > e)
+    return bool(np.all(ok | ~fires))

@@ -117,8 +117,29 @@ int gemhip_gf_plan_get_embedding(gemhip_gf_plan_t plan, float *X_host);
 /* Device pointer of the CURRENT table (the one holding the latest sweep). */
 int gemhip_gf_plan_current(gemhip_gf_plan_t plan, void **dX);
 /* info (8 int64): {updates_per_sweep, rows_per_sweep, levels, n, d,
- * algorithmic_bytes_per_sweep, rows per wavefront of the largest level's launch, 0} */
+ * algorithmic_bytes_per_sweep, rows per wavefront of the largest level's launch, 1 on a unit schedule
+ * (gemhip_gf_plan_create_any_order; rows_per_sweep then counts units) else 0} */
 int gemhip_gf_plan_info(gemhip_gf_plan_t plan, int64_t *info);
+/* Any edge order, exactly as gf.cpp:152-164 walks it (DESIGN.md "GF: any edge order").  A list gemhip_gf_plan_create accepts gets exactly that
+ * plan (all rows; same levels, kernels and speed).  Any other list -- a shuffled file, two sorted files concatenated, edges appended later -- gets a
+ * UNIT schedule: a unit is a run of one row's edges that one wavefront applies in file order (gf_sweep_units_kernel), units are placed in levels so
+ * that two edges touching a row one of them writes run in file order; one launch per level, in stream order.  flags bit 0 forces the unit schedule
+ * on a list the row schedule represents (tests, A/B); the tables are bit-identical either way.  The plan works with every gemhip_gf_plan_* call;
+ * on a unit plan gemhip_gf_plan_info reports {.., units, levels, .., info[6] = 1, info[7] = 1}, and set_rows_per_wave / set_fused_sweeps are accepted
+ * and change nothing.  A unit schedule covers all rows of one device (no row range).  Like every plan it needs the two tables to agree on the rows
+ * that never fire: set_embedding / init_embedding fill both tables (own or bound) with the same values; after gemhip_gf_plan_bind alone that is
+ * the caller's promise ("both must hold the same initial embedding").  Needs fewer than 2^31 firing edges. */
+int gemhip_gf_plan_create_any_order(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, const float *w, int32_t d, int32_t flags,
+                                    gemhip_gf_plan_t *out);
+/* Unit plans: run every maximal run of two or more consecutive levels of at most max_units units (0 = off, at most 16) in ONE launch of one
+ * 16-wavefront workgroup, with a workgroup barrier where the level loop has a kernel boundary.  Launches per sweep = (levels with more than
+ * max_units units) + (runs of consecutive smaller levels).  Bit-identical tables either way.  Accepted without effect on a row plan. */
+int gemhip_gf_plan_set_fused_levels(gemhip_gf_plan_t plan, int32_t max_units);
+/* The unit schedule of a list, on the host alone (no HIP call): per edge its unit (numbered in file order of first edge), the unit's level,
+ * and flags (bit 0: the neighbour is read from the working table X_new, bit 1: the unit loads its own row from X_new); edges that do not fire
+ * (dst <= src) get -1 in all three.  counts = {units, levels}.  Any output may be NULL. */
+int gemhip_gf_any_order_schedule(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, int32_t *unit_out, int32_t *level_out,
+                                 int32_t *flags_out, int64_t *counts);
 /* gf.cpp:94-113 objective on the device table: out = {f1, f2}. `m` edges as in
  * plan_create but over ALL edges (no dst>src filter), like the reference. */
 int gemhip_gf_objective(int64_t n, int64_t m, const int32_t *src,
