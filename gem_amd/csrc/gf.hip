@@ -24,7 +24,10 @@
 //
 // HBM traffic per sweep (algorithmic, d=128): 512 B read + 512 B write per active
 // row, 512 B gather + 8 B (col,w) per update.
+//
+// The host planning (which edge orders this can represent, levels, hub rows, the unit schedule of any other order) is plain C++ in gf_plan.hip.
 #include "common.hpp"
+#include "gf_plan.hpp"
 #include <hip/hip_cooperative_groups.h>
 #include <cstdlib>
 #include <vector>
@@ -33,9 +36,12 @@
 
 using namespace gemhip;
 
+namespace { struct gf_launchers; }
+
 struct gemhip_gf_plan {
     int64_t n = 0, d = 0, nrows = 0, nupd = 0;
     int device = 0;
+    const gf_launchers *fn = nullptr; // the kernels instantiated for d (gf_launchers_for)
     std::vector<int64_t> level_off;   // rows of level L are [level_off[L], level_off[L+1])
     std::vector<int64_t> level_hubs;  // ... of which the first level_hubs[L] are hub rows (gf_hub_kernel)
     std::vector<int64_t> level_maxlen;  // longest non-hub row of the level, in firing edges (the rows-per-wavefront rule looks at it)
@@ -59,14 +65,11 @@ struct gemhip_gf_plan {
     // Auto: 2 on the K-rows-per-wavefront kernel (the big levels), 0 on the one-row kernel (small, L2-resident levels, where nothing needs evicting).
     // A hint only: results are bit-identical either way.
     int nt_store = getenv("GEMHIP_GF_NT_STORE") ? atoi(getenv("GEMHIP_GF_NT_STORE")) : -1;
-    // Unit schedule (gemhip_gf_plan_create_any_order on a list the row schedule cannot represent).  The same arrays, read differently: d_rows holds one
-    // entry per UNIT (a run of one row's edges), row id | (1u<<31 if the unit loads its own row from X_new: the row was already written this sweep),
-    // d_ptr / d_col / d_w its edges in file order, level_off the units of each level; nrows counts units.  level_hubs / level_maxlen stay empty.
+    // Unit schedule (gemhip_gf_plan_create_any_order on a list the row schedule cannot represent): the same arrays, read differently (GfHostPlan);
+    // nrows counts units.
     bool units = false;
-    int fused_levels = 0;             // gemhip_gf_plan_set_fused_levels: consecutive levels of at most this many units share one launch (0 = off)
     DevBuf<int64_t> d_level_off;      // level_off on the device (gf_units_fused_kernel walks it)
-    struct seg { int l0, l1; bool fused; };
-    std::vector<seg> segs;            // the launches of one sweep: [l0, l1) is one level, or a fused run of small levels
+    std::vector<GfSeg> segs;          // the launches of one sweep (gf_units_segments; gemhip_gf_plan_set_fused_levels recomputes them)
 };
 
 namespace {
@@ -173,6 +176,36 @@ __device__ __forceinline__ void gf_chunk(float (&xi)[NV][VEC], uint32_t cj, floa
     }
 }
 
+// neighbour rows in flight on FULL 64-edge chunks.  Hub rows (power-law graphs) are one long dependent chain of updates: only memory latency can be
+// hidden, so full chunks keep GF_PREFETCH_DEEP / NV (at least GF_PREFETCH) neighbour rows in flight instead of GF_PREFETCH
+template <int NV> constexpr int GF_DEEP = (GF_PREFETCH_DEEP / NV) >= GF_PREFETCH ? (GF_PREFETCH_DEEP / NV) : GF_PREFETCH;
+
+// one row's chunk of `cnt` edges whose (col, w) lane `k` holds for edge k
+template <int VEC, int NV>
+__device__ __forceinline__ void gf_apply_chunk(float (&xi)[NV][VEC], uint32_t cj, float wj, int cnt, const float *Xold, const float *Xnew, int d, int lane,
+                                               float eta, float regu)
+{
+    if (cnt == WAVE) gf_chunk<VEC, NV, GF_DEEP<NV>>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
+    else gf_chunk<VEC, NV, GF_PREFETCH>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
+}
+
+// a plan stream (col, w, row ids, offsets), read once per sweep: bit 2 of the plan's nt_store asks for the non-temporal hint
+template <typename T> __device__ __forceinline__ T gf_ld_stream(const T *p, int nt) { return (nt & 4) ? __builtin_nontemporal_load(p) : *p; }
+
+// THE row body of every wave-per-row kernel: the edges [e, e1) of one row applied to xi in edge order, 64 at a time
+template <int VEC, int NV>
+__device__ __forceinline__ void gf_row_edges(float (&xi)[NV][VEC], int64_t e, int64_t e1, const uint32_t *__restrict__ col, const float *__restrict__ w,
+                                             const float *Xold, const float *Xnew, int d, int lane, float eta, float regu, int nt)
+{
+    for (; e < e1; e += WAVE) {
+        const int cnt = (int)((e1 - e) < (int64_t)WAVE ? (e1 - e) : (int64_t)WAVE);
+        // coalesced read of up to 64 (col, w) pairs of this row; broadcast later with v_readlane
+        const uint32_t cj = lane < cnt ? gf_ld_stream(col + e + lane, nt) : 0u;
+        const float wj = lane < cnt ? gf_ld_stream(w + e + lane, nt) : 0.f;
+        gf_apply_chunk<VEC, NV>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
+    }
+}
+
 // One sweep over the rows of one level.  One wavefront per row.
 template <int VEC, int NV>
 __global__ __launch_bounds__(GF_BLOCK) void gf_sweep_kernel(const int32_t *__restrict__ rows, const int64_t *__restrict__ ptr,
@@ -192,18 +225,7 @@ __global__ __launch_bounds__(GF_BLOCK) void gf_sweep_kernel(const int32_t *__res
     const float *pi = Xold + (int64_t)i * d;
 #pragma unroll
     for (int c = 0; c < NV; ++c) load_own_row<VEC>(pi, d, lane, c, xi[c], nt);
-
-    // hub rows (power-law graphs) are one long dependent chain of updates: only memory latency can be hidden, so full
-    // 64-edge chunks keep GF_PREFETCH_DEEP neighbour rows in flight instead of GF_PREFETCH
-    constexpr int DEEP = (GF_PREFETCH_DEEP / NV) >= GF_PREFETCH ? (GF_PREFETCH_DEEP / NV) : GF_PREFETCH;
-    for (int64_t e = e0; e < e1; e += WAVE) {
-        const int cnt = (int)((e1 - e) < (int64_t)WAVE ? (e1 - e) : (int64_t)WAVE);
-        // coalesced read of up to 64 (col, w) pairs of this row; broadcast later with v_readlane
-        const uint32_t cj = lane < cnt ? col[e + lane] : 0u;
-        const float wj = lane < cnt ? w[e + lane] : 0.f;
-        if (cnt == WAVE) gf_chunk<VEC, NV, DEEP>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
-        else gf_chunk<VEC, NV, GF_PREFETCH>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
-    }
+    gf_row_edges<VEC, NV>(xi, e0, e1, col, w, Xold, Xnew, d, lane, eta, regu, 0);
     store_row<VEC, NV>(Xnew + (int64_t)i * d, d, lane, xi, nt);
 }
 
@@ -222,7 +244,6 @@ __global__ __launch_bounds__(GF_BLOCK) void gf_sweeps_coop_kernel(const int32_t 
     const int wave = threadIdx.x >> 6;
     const int64_t nslots = (int64_t)gridDim.x * GF_WAVES;
     const int64_t first = xcd_contiguous_block(blockIdx.x, gridDim.x) * GF_WAVES + wave;
-    constexpr int DEEP = (GF_PREFETCH_DEEP / NV) >= GF_PREFETCH ? (GF_PREFETCH_DEEP / NV) : GF_PREFETCH;
     for (int s = 0; s < nsweeps; ++s) {
         const float *Xold = (s & 1) ? X1 : X0;
         float *Xnew = (s & 1) ? X0 : X1;
@@ -233,13 +254,7 @@ __global__ __launch_bounds__(GF_BLOCK) void gf_sweeps_coop_kernel(const int32_t 
             const float *pi = Xold + (int64_t)i * d;
 #pragma unroll
             for (int c = 0; c < NV; ++c) load_row<VEC>(pi, d, lane, c, xi[c]);
-            for (int64_t e = e0; e < e1; e += WAVE) {
-                const int cnt = (int)((e1 - e) < (int64_t)WAVE ? (e1 - e) : (int64_t)WAVE);
-                const uint32_t cj = lane < cnt ? col[e + lane] : 0u;
-                const float wj = lane < cnt ? w[e + lane] : 0.f;
-                if (cnt == WAVE) gf_chunk<VEC, NV, DEEP>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
-                else gf_chunk<VEC, NV, GF_PREFETCH>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
-            }
+            gf_row_edges<VEC, NV>(xi, e0, e1, col, w, Xold, Xnew, d, lane, eta, regu, 0);
             store_row<VEC, NV>(Xnew + (int64_t)i * d, d, lane, xi, 0);
         }
         grid.sync();
@@ -292,25 +307,25 @@ __global__ __launch_bounds__(GF_BLOCK) void gf_sweep_rows_kernel(const int32_t *
     const int nk = (int)((nrows - first) < (int64_t)K ? (nrows - first) : (int64_t)K);
     int32_t rv = 0; int64_t pa = 0, pb = 0;
     if (lane < nk) {
-        if (nt & 4) { rv = __builtin_nontemporal_load(rows + row0 + first + lane); pa = __builtin_nontemporal_load(ptr + row0 + first + lane); pb = __builtin_nontemporal_load(ptr + row0 + first + lane + 1); }
-        else { rv = rows[row0 + first + lane]; pa = ptr[row0 + first + lane]; pb = ptr[row0 + first + lane + 1]; }
+        rv = gf_ld_stream(rows + row0 + first + lane, nt);
+        pa = gf_ld_stream(ptr + row0 + first + lane, nt); pb = gf_ld_stream(ptr + row0 + first + lane + 1, nt);
     }
-    auto ld_col = [&](int64_t e) -> uint32_t { return (nt & 4) ? __builtin_nontemporal_load(col + e) : col[e]; };
-    auto ld_w = [&](int64_t e) -> float { return (nt & 4) ? __builtin_nontemporal_load(w + e) : w[e]; };
     auto lane64 = [&](int64_t v, int k) -> int64_t {
         const uint32_t lo = bcast_lane((uint32_t)v, k), hi = bcast_lane((uint32_t)((uint64_t)v >> 32), k);
         return (int64_t)(((uint64_t)hi << 32) | lo);
     };
-    constexpr int DEEP = (GF_PREFETCH_DEEP / NV) >= GF_PREFETCH ? (GF_PREFETCH_DEEP / NV) : GF_PREFETCH;
-    // row 0: first (col, w) chunk and X_i
-    int32_t i_n = bcast_lane(rv, 0);
-    int64_t e0_n = lane64(pa, 0), e1_n = lane64(pb, 0);
-    int cnt_n = (int)((e1_n - e0_n) < (int64_t)WAVE ? (e1_n - e0_n) : (int64_t)WAVE);
-    uint32_t cj_n = lane < cnt_n ? ld_col(e0_n + lane) : 0u;
-    float wj_n = lane < cnt_n ? ld_w(e0_n + lane) : 0.f;
+    int32_t i_n; int64_t e0_n, e1_n; int cnt_n; uint32_t cj_n; float wj_n;
     float xi_n[NV][VEC];
+    auto fetch = [&](int k) {                            // row k of this wavefront: its id and offsets, then its first (col, w) chunk and X_i
+        i_n = bcast_lane(rv, k);
+        e0_n = lane64(pa, k); e1_n = lane64(pb, k);
+        cnt_n = (int)((e1_n - e0_n) < (int64_t)WAVE ? (e1_n - e0_n) : (int64_t)WAVE);
+        cj_n = lane < cnt_n ? gf_ld_stream(col + e0_n + lane, nt) : 0u;
+        wj_n = lane < cnt_n ? gf_ld_stream(w + e0_n + lane, nt) : 0.f;
 #pragma unroll
-    for (int c = 0; c < NV; ++c) load_own_row<VEC>(Xold + (int64_t)i_n * d, d, lane, c, xi_n[c], nt);
+        for (int c = 0; c < NV; ++c) load_own_row<VEC>(Xold + (int64_t)i_n * d, d, lane, c, xi_n[c], nt);
+    };
+    fetch(0);
     for (int k = 0; k < nk; ++k) {
         const int32_t i = i_n;
         const int64_t e0 = e0_n, e1 = e1_n;
@@ -322,61 +337,34 @@ __global__ __launch_bounds__(GF_BLOCK) void gf_sweep_rows_kernel(const int32_t *
         for (int c = 0; c < NV; ++c)
 #pragma unroll
             for (int v = 0; v < VEC; ++v) xi[c][v] = xi_n[c][v];
-        if (k + 1 < nk) {                                // the next row's inputs travel while this row is trained
-            i_n = bcast_lane(rv, k + 1);
-            e0_n = lane64(pa, k + 1); e1_n = lane64(pb, k + 1);
-            cnt_n = (int)((e1_n - e0_n) < (int64_t)WAVE ? (e1_n - e0_n) : (int64_t)WAVE);
-            cj_n = lane < cnt_n ? ld_col(e0_n + lane) : 0u;
-            wj_n = lane < cnt_n ? ld_w(e0_n + lane) : 0.f;
-#pragma unroll
-            for (int c = 0; c < NV; ++c) load_own_row<VEC>(Xold + (int64_t)i_n * d, d, lane, c, xi_n[c], nt);
-        }
-        if (cnt0 == WAVE) gf_chunk<VEC, NV, DEEP>(xi, cj0, wj0, cnt0, Xold, Xnew, d, lane, eta, regu);
-        else if (cnt0 > 0) gf_chunk<VEC, NV, GF_PREFETCH>(xi, cj0, wj0, cnt0, Xold, Xnew, d, lane, eta, regu);
-        for (int64_t e = e0 + WAVE; e < e1; e += WAVE) {
-            const int cnt = (int)((e1 - e) < (int64_t)WAVE ? (e1 - e) : (int64_t)WAVE);
-            const uint32_t cj = lane < cnt ? ld_col(e + lane) : 0u;
-            const float wj = lane < cnt ? ld_w(e + lane) : 0.f;
-            if (cnt == WAVE) gf_chunk<VEC, NV, DEEP>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
-            else gf_chunk<VEC, NV, GF_PREFETCH>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
-        }
+        if (k + 1 < nk) fetch(k + 1);                    // the next row's inputs travel while this row is trained
+        if (cnt0 > 0) gf_apply_chunk<VEC, NV>(xi, cj0, wj0, cnt0, Xold, Xnew, d, lane, eta, regu);      // the chunk that travelled with the row before
+        gf_row_edges<VEC, NV>(xi, e0 + WAVE, e1, col, w, Xold, Xnew, d, lane, eta, regu, nt);
         store_row<VEC, NV>(Xnew + (int64_t)i * d, d, lane, xi, nt);
     }
 }
 
-// rows per wavefront of a level with `nrows` rows: 1 (gf_sweep_kernel) until every resident wave slot of the chip (256 CUs x 32 waves) has two rows
-// to work on, then up to GEMHIP_GF_ROWS_PER_WAVE (default 8; read once): a level of 946 188 rows (SBM 1M/10M) runs 8 rows per wave
-int gf_rows_per_wave(int64_t nrows)
+// rows per wavefront of the sweep launch over `nrows` rows of level l (gf_level_rows_per_wave; at most GEMHIP_GF_ROWS_PER_WAVE, default 8, read once)
+int gf_rows_per_wave(const gemhip_gf_plan *p, size_t l, int64_t nrows)
 {
     static const int kmax = getenv("GEMHIP_GF_ROWS_PER_WAVE") ? std::max(1, std::min(64, atoi(getenv("GEMHIP_GF_ROWS_PER_WAVE")))) : 8;
-    const int64_t k = nrows / (2 * 256 * 32);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(k, kmax));
+    return gf_level_rows_per_wave(p->rows_per_wave, l < p->level_maxlen.size() ? p->level_maxlen[l] : 0, nrows, kmax);
 }
 
+// workgroups of GF_WAVES wavefronts for `waves` of them, rounded up to a multiple of 8 so the XCD-contiguous map covers every slot
+dim3 gf_grid(int64_t waves) { return dim3((unsigned)(((waves + GF_WAVES - 1) / GF_WAVES + NUM_XCD - 1) / NUM_XCD * NUM_XCD)); }
+
+// the rows [row0, row0 + nrows) of level l
 template <int VEC, int NV>
-void launch_sweep(const gemhip_gf_plan *p, int64_t row0, int64_t nrows, const float *Xold, float *Xnew, float eta, float regu,
-                  hipStream_t s)
+void launch_sweep(const gemhip_gf_plan *p, int l, int64_t row0, int64_t nrows, const float *Xold, float *Xnew, float eta, float regu, hipStream_t s)
 {
-    // K rows per wavefront pays where rows are short and alike (SBM: 548 against 579 us per sweep at 1M/10M); on a power-law level a wavefront that
-    // draws a few long rows among its K holds the launch up (R-MAT scale 22: 6.99 against 6.52 ms) -- levels with rows of more than two 64-edge
-    // chunks keep one row per wavefront
-    int64_t maxlen = 0;
-    for (size_t l = 0; l + 1 < p->level_off.size(); ++l)
-        if (row0 >= p->level_off[l] && row0 < p->level_off[l + 1]) maxlen = p->level_maxlen.size() > l ? p->level_maxlen[l] : 0;
-    const int K = p->rows_per_wave > 0 ? p->rows_per_wave : (maxlen > 2 * WAVE ? 1 : gf_rows_per_wave(nrows));
-    if (K > 1) {
-        const int64_t waves = (nrows + K - 1) / K;
-        const int64_t blocks = (waves + GF_WAVES - 1) / GF_WAVES;
-        const int64_t grid = (blocks + NUM_XCD - 1) / NUM_XCD * NUM_XCD;
-        hipLaunchKernelGGL((gf_sweep_rows_kernel<VEC, NV>), dim3((unsigned)grid), dim3(GF_BLOCK), 0, s, p->d_rows, p->d_ptr, p->d_col,
+    const int K = gf_rows_per_wave(p, (size_t)l, nrows);
+    if (K > 1)
+        hipLaunchKernelGGL((gf_sweep_rows_kernel<VEC, NV>), gf_grid((nrows + K - 1) / K), dim3(GF_BLOCK), 0, s, p->d_rows, p->d_ptr, p->d_col,
                            p->d_w, Xold, Xnew, row0, nrows, (int)p->d, eta, regu, K, p->nt_store < 0 ? 2 : p->nt_store);
-        return;
-    }
-    const int64_t blocks = (nrows + GF_WAVES - 1) / GF_WAVES;
-    // round the grid up to a multiple of 8 so the XCD-contiguous map covers every slot
-    const int64_t grid = (blocks + NUM_XCD - 1) / NUM_XCD * NUM_XCD;
-    hipLaunchKernelGGL((gf_sweep_kernel<VEC, NV>), dim3((unsigned)grid), dim3(GF_BLOCK), 0, s, p->d_rows, p->d_ptr, p->d_col,
-                       p->d_w, Xold, Xnew, row0, nrows, (int)p->d, eta, regu, p->nt_store < 0 ? 0 : p->nt_store);
+    else
+        hipLaunchKernelGGL((gf_sweep_kernel<VEC, NV>), gf_grid(nrows), dim3(GF_BLOCK), 0, s, p->d_rows, p->d_ptr, p->d_col,
+                           p->d_w, Xold, Xnew, row0, nrows, (int)p->d, eta, regu, p->nt_store < 0 ? 0 : p->nt_store);
 }
 
 // Hub rows (power-law graphs).  The updates of one row are one dependent chain (exact Gauss-Seidel): a wave that also fetches its
@@ -443,15 +431,7 @@ __global__ __launch_bounds__((NP + 1) * 64) void gf_hub_kernel(const int32_t *__
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (lane == 0) gf_flag_st(&done, t + 1);
         }
-        float *po = Xnew + (int64_t)i * d;
-#pragma unroll
-        for (int c = 0; c < NV; ++c) {
-            const int idx = (c * WAVE + lane) * VEC;
-            if (idx < d) {
-                if constexpr (VEC == 2) *reinterpret_cast<float2 *>(po + idx) = make_float2(xi[c][0], xi[c][1]);
-                else po[idx] = xi[c][0];
-            }
-        }
+        store_row<VEC, NV>(Xnew + (int64_t)i * d, d, lane, xi, 0);
     } else {
         for (int t = wave - 1; t < nb; t += NP) {
             const int sb = t % NBATCH;
@@ -497,46 +477,6 @@ void launch_hub(const gemhip_gf_plan *p, int64_t row0, int64_t nhub, const float
         hipLaunchKernelGGL((gf_hub_kernel<VEC, NV, 3>), dim3((unsigned)nhub), dim3(256), 0, s, p->d_rows, p->d_ptr, p->d_col, p->d_w, Xold, Xnew, row0,
                            (int)p->d, eta, regu);
 }
-using hub_fn = void (*)(const gemhip_gf_plan *, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
-hub_fn pick_hub(int d)
-{
-    if (d % 2 == 0) {
-        const int nv = (d + 127) / 128;
-        return nv <= 1 ? launch_hub<2, 1> : nv <= 2 ? launch_hub<2, 2> : nv <= 4 ? launch_hub<2, 4> : nv <= 8 ? launch_hub<2, 8> : nullptr;
-    }
-    const int nv = (d + 63) / 64;
-    return nv <= 1 ? launch_hub<1, 1> : nv <= 2 ? launch_hub<1, 2> : nv <= 4 ? launch_hub<1, 4> : nv <= 8 ? launch_hub<1, 8> : nullptr;
-}
-
-using sweep_fn = void (*)(const gemhip_gf_plan *, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
-using coop_fn = int (*)(const gemhip_gf_plan *, float *, float *, float, float, int, hipStream_t);
-coop_fn pick_coop(int d)
-{
-    if (d % 2 == 0) {
-        const int nv = (d + 127) / 128;
-        return nv <= 1 ? launch_coop<2, 1> : nv <= 2 ? launch_coop<2, 2> : nv <= 4 ? launch_coop<2, 4> : nv <= 8 ? launch_coop<2, 8> : nullptr;
-    }
-    const int nv = (d + 63) / 64;
-    return nv <= 1 ? launch_coop<1, 1> : nv <= 2 ? launch_coop<1, 2> : nv <= 4 ? launch_coop<1, 4> : nv <= 8 ? launch_coop<1, 8> : nullptr;
-}
-
-sweep_fn pick_sweep(int d)
-{
-    if (d % 2 == 0) {
-        const int nv = (d + 127) / 128;
-        if (nv <= 1) return launch_sweep<2, 1>;
-        if (nv <= 2) return launch_sweep<2, 2>;
-        if (nv <= 4) return launch_sweep<2, 4>;
-        if (nv <= 8) return launch_sweep<2, 8>;
-        return nullptr;
-    }
-    const int nv = (d + 63) / 64;
-    if (nv <= 1) return launch_sweep<1, 1>;
-    if (nv <= 2) return launch_sweep<1, 2>;
-    if (nv <= 4) return launch_sweep<1, 4>;
-    if (nv <= 8) return launch_sweep<1, 8>;
-    return nullptr;
-}
 
 // ---- unit schedule (any edge order; gemhip_gf_plan_create_any_order).  A UNIT is a run of one row's edges that one wavefront applies in file order:
 // it loads the row once -- from X_new when the row was already written in this sweep (bit 31 of its entry), else from X_old --, gathers every
@@ -554,14 +494,7 @@ __device__ __forceinline__ void gf_unit_body(const uint32_t *__restrict__ units,
     const float *pi = ((ru >> 31) ? Xnew : Xold) + i * d;
 #pragma unroll
     for (int c = 0; c < NV; ++c) load_row<VEC>(pi, d, lane, c, xi[c]);
-    constexpr int DEEP = (GF_PREFETCH_DEEP / NV) >= GF_PREFETCH ? (GF_PREFETCH_DEEP / NV) : GF_PREFETCH;
-    for (int64_t e = e0; e < e1; e += WAVE) {
-        const int cnt = (int)((e1 - e) < (int64_t)WAVE ? (e1 - e) : (int64_t)WAVE);
-        const uint32_t cj = lane < cnt ? col[e + lane] : 0u;
-        const float wj = lane < cnt ? w[e + lane] : 0.f;
-        if (cnt == WAVE) gf_chunk<VEC, NV, DEEP>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
-        else gf_chunk<VEC, NV, GF_PREFETCH>(xi, cj, wj, cnt, Xold, Xnew, d, lane, eta, regu);
-    }
+    gf_row_edges<VEC, NV>(xi, e0, e1, col, w, Xold, Xnew, d, lane, eta, regu, 0);
     store_row<VEC, NV>(Xnew + i * d, d, lane, xi, 0);
 }
 
@@ -601,10 +534,8 @@ __global__ __launch_bounds__(GF_FUSED_WAVES * WAVE) void gf_units_fused_kernel(c
 template <int VEC, int NV>
 void launch_units(const gemhip_gf_plan *p, int64_t unit0, int64_t nunits, const float *Xold, float *Xnew, float eta, float regu, hipStream_t s)
 {
-    const int64_t blocks = (nunits + GF_WAVES - 1) / GF_WAVES;
-    const int64_t grid = (blocks + NUM_XCD - 1) / NUM_XCD * NUM_XCD;           // a multiple of 8: the XCD-contiguous map covers every slot
     const int32_t *units = p->d_rows;
-    hipLaunchKernelGGL((gf_sweep_units_kernel<VEC, NV>), dim3((unsigned)grid), dim3(GF_BLOCK), 0, s, (const uint32_t *)units, p->d_ptr, p->d_col,
+    hipLaunchKernelGGL((gf_sweep_units_kernel<VEC, NV>), gf_grid(nunits), dim3(GF_BLOCK), 0, s, (const uint32_t *)units, p->d_ptr, p->d_col,
                        p->d_w, Xold, Xnew, unit0, nunits, (int)p->d, eta, regu);
 }
 template <int VEC, int NV>
@@ -614,95 +545,30 @@ void launch_units_fused(const gemhip_gf_plan *p, int l0, int l1, const float *Xo
     hipLaunchKernelGGL((gf_units_fused_kernel<VEC, NV>), dim3(1), dim3(GF_FUSED_WAVES * WAVE), 0, s, (const uint32_t *)units, p->d_ptr, p->d_col,
                        p->d_w, p->d_level_off, Xold, Xnew, l0, l1, (int)p->d, eta, regu);
 }
-struct units_fns {
-    void (*level)(const gemhip_gf_plan *, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
-    void (*fused)(const gemhip_gf_plan *, int, int, const float *, float *, float, float, hipStream_t);
+
+// ---- one dispatch: the launchers of the (VEC, NV) instantiation a width d runs on.  A lane holds VEC floats of each of NV 64-lane chunks of a row:
+// even d -> float2 per lane and ceil(d / 128) chunks, odd d -> one float and ceil(d / 64) chunks, the chunk count rounded up to 1, 2, 4 or 8.
+struct gf_launchers {
+    void (*sweep)(const gemhip_gf_plan *, int, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
+    void (*hub)(const gemhip_gf_plan *, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
+    int (*coop)(const gemhip_gf_plan *, float *, float *, float, float, int, hipStream_t);
+    void (*units)(const gemhip_gf_plan *, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
+    void (*units_fused)(const gemhip_gf_plan *, int, int, const float *, float *, float, float, hipStream_t);
 };
-template <int VEC, int NV> units_fns units_of() { return {launch_units<VEC, NV>, launch_units_fused<VEC, NV>}; }
-units_fns pick_units(int d)      // the instantiations of pick_sweep
+template <int VEC, int NV> const gf_launchers *gf_launchers_of()
 {
-    if (d % 2 == 0) {
-        const int nv = (d + 127) / 128;
-        return nv <= 1 ? units_of<2, 1>() : nv <= 2 ? units_of<2, 2>() : nv <= 4 ? units_of<2, 4>() : units_of<2, 8>();
-    }
-    const int nv = (d + 63) / 64;
-    return nv <= 1 ? units_of<1, 1>() : nv <= 2 ? units_of<1, 2>() : nv <= 4 ? units_of<1, 4>() : units_of<1, 8>();
+    static const gf_launchers L = {launch_sweep<VEC, NV>, launch_hub<VEC, NV>, launch_coop<VEC, NV>, launch_units<VEC, NV>, launch_units_fused<VEC, NV>};
+    return &L;
 }
-
-// the launches of one sweep of a unit plan: every maximal run of two or more consecutive levels of at most fused_levels units is one launch
-// (gf_units_fused_kernel), every other level one (gf_sweep_units_kernel)
-void gf_units_segments(gemhip_gf_plan *p)
+template <int VEC> const gf_launchers *gf_launchers_of_chunks(int nv)
 {
-    p->segs.clear();
-    const int nlevels = (int)p->level_off.size() - 1;
-    auto small = [&](int l) { return p->fused_levels > 0 && p->level_off[l + 1] - p->level_off[l] <= p->fused_levels; };
-    for (int l = 0; l < nlevels;) {
-        int e = l + 1;
-        if (small(l)) while (e < nlevels && small(e)) ++e;
-        p->segs.push_back({l, e, e - l > 1});
-        l = e;
-    }
+    return nv <= 1 ? gf_launchers_of<VEC, 1>() : nv <= 2 ? gf_launchers_of<VEC, 2>() : nv <= 4 ? gf_launchers_of<VEC, 4>() : nv <= 8 ? gf_launchers_of<VEC, 8>() : nullptr;
 }
-
-// The any-order rule.  Walk the firing edges in file order; per row r: lastW[r] = level of the last unit that wrote r in this sweep (-1: not written
-// yet, the row is read from X_old), lastR[r] = highest level of a read of the CURRENT X_new version of r (-1 after every write of r; reads of X_old
-// never count: X_old is not written during the sweep), lastU[r] = r's latest unit.  Edge (i, j) must run after j's last write when it reads X_new[j]
-// (read after write) and after every read of i's current intermediate version (write after read): c is the higher of the two.  It joins i's latest
-// unit when that unit already runs after c, else it opens a unit one level above c and above i's last write.  Two firing edges that touch a common row
-// which one of them writes therefore sit in strictly ordered levels, or in one unit in file order: the result equals the sequential loop.  O(n + m).
-struct gf_unit_schedule {
-    std::vector<int32_t> unit_of;         // per edge: its unit (creation order), -1 = does not fire
-    std::vector<uint8_t> nb_new;          // per edge: the neighbour is read from X_new
-    std::vector<int32_t> row, level;      // per unit
-    std::vector<uint8_t> own_new;         // per unit: its own row is loaded from X_new
-    int32_t nlevels = 0;
-    int64_t nupd = 0;
-};
-int gf_schedule_units(const char *who, int64_t n, int64_t m, const int32_t *src, const int32_t *dst, gf_unit_schedule &S)
+// nullptr: d unsupported (supported: even d <= 1024, odd d <= 512)
+const gf_launchers *gf_launchers_for(int d)
 {
-    std::vector<int32_t> lastW(n, -1), lastR(n, -1), lastU(n, -1);
-    S.unit_of.assign(m, -1); S.nb_new.assign(m, 0);
-    for (int64_t e = 0; e < m; ++e) {
-        const int32_t i = src[e], j = dst[e];
-        GEMHIP_REQUIRE(i >= 0 && i < n && j >= 0 && j < n, "%s: edge %lld = (%d,%d) outside [0,%lld)", who, (long long)e, i, j, (long long)n);
-        if (j <= i) continue;                        // does not fire (gf.py:95, gf.cpp:157)
-        GEMHIP_REQUIRE(S.row.size() < (size_t)0x7fffffff, "%s: more than 2^31 - 1 units", who);
-        const bool jn = lastW[j] >= 0;
-        const int32_t c = std::max(lastW[j], lastR[i]);
-        int32_t lv, u;
-        if (lastW[i] >= 0 && c < lastW[i]) { u = lastU[i]; lv = lastW[i]; }
-        else {
-            lv = std::max(c, lastW[i]) + 1;
-            u = (int32_t)S.row.size();
-            S.row.push_back(i); S.level.push_back(lv); S.own_new.push_back(lastW[i] >= 0);
-            lastU[i] = u;
-            S.nlevels = std::max(S.nlevels, lv + 1);
-        }
-        S.unit_of[e] = u; S.nb_new[e] = jn; ++S.nupd;
-        if (jn) lastR[j] = std::max(lastR[j], lv);
-        lastW[i] = lv; lastR[i] = -1;
-    }
-    return GEMHIP_OK;
-}
-
-// true when gemhip_gf_plan_create accepts the list: every firing edge reads a row that has had all or none of its updates of the sweep (the test of
-// gemhip_gf_plan_create, which also words the refusal).  A list with an endpoint out of range counts as accepted: that call reports it.
-bool gf_rows_schedule_represents(int64_t n, int64_t m, const int32_t *src, const int32_t *dst)
-{
-    std::vector<int64_t> first_t(n, -1), last_t(n, -1);
-    for (int64_t e = 0; e < m; ++e) {
-        const int32_t i = src[e], j = dst[e];
-        if (i < 0 || i >= n || j < 0 || j >= n) return true;
-        if (j <= i) continue;
-        if (first_t[i] < 0) first_t[i] = e;
-        last_t[i] = e;
-    }
-    for (int64_t e = 0; e < m; ++e) {
-        const int32_t i = src[e], j = dst[e];
-        if (j <= i || first_t[j] < 0) continue;
-        if (!(first_t[j] < first_t[i] ? last_t[j] < e : first_t[j] > e)) return false;
-    }
-    return true;
+    if (d < 1) return nullptr;
+    return d % 2 == 0 ? gf_launchers_of_chunks<2>((d + 127) / 128) : gf_launchers_of_chunks<1>((d + 63) / 64);
 }
 
 // 0.01*N(0,1)-style init: thread t fills elements 4t..4t+3 from one Philox block.
@@ -753,133 +619,73 @@ __global__ __launch_bounds__(256) void gf_objective_kernel(const int32_t *__rest
 }  // namespace
 
 // ------------------------------------------------------------------- host API
-extern "C" int gemhip_gf_plan_create(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, const float *w, int32_t d,
-                                     int64_t row_begin, int64_t row_end, gemhip_gf_plan_t *out)
+constexpr int GF_FUSED_LEVELS_DEFAULT = 16;
+
+// what both creators check before they plan
+static int gf_validate(const char *who, int64_t n, int64_t m, const int32_t *src, const int32_t *dst, gemhip_gf_plan_t *out)
 {
-    GEMHIP_REQUIRE(out != nullptr, "gf_plan_create: out is NULL");
+    GEMHIP_REQUIRE(out != nullptr, "%s: out is NULL", who);
     *out = nullptr;
-    GEMHIP_REQUIRE(n > 0 && n < (int64_t)0x7fffffff, "gf_plan_create: n=%lld out of range", (long long)n);
-    GEMHIP_REQUIRE(m >= 0 && (m == 0 || (src && dst)), "gf_plan_create: bad edge arrays");
-    GEMHIP_REQUIRE(d >= 1, "gf_plan_create: d=%d", d);
-    GEMHIP_REQUIRE(pick_sweep(d) != nullptr, "gf_plan_create: d=%d unsupported (even d <= 1024, odd d <= 512)", d);
-    GEMHIP_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= n, "gf_plan_create: bad row range");
+    GEMHIP_REQUIRE(n > 0 && n < (int64_t)0x7fffffff, "%s: n=%lld out of range", who, (long long)n);
+    GEMHIP_REQUIRE(m >= 0 && (m == 0 || (src && dst)), "%s: bad edge arrays", who);
+    return GEMHIP_OK;
+}
 
-    // 1. rows in the order the reference first visits them; keep only firing edges (dst > src) of owned rows.
-    const double t_host0 = phase_now();
-    std::vector<int32_t> pos(n, -1);          // pos[i] = rank of row i among firing source rows (reference order)
-    std::vector<int32_t> order;               // row ids by pos
-    std::vector<int64_t> deg;
-    // The plan gives a source row ONE wavefront and all of its firing edges in one go, reading X_new[j] for neighbours whose
-    // row comes earlier in first-visit order and X_old[j] otherwise.  That equals the reference's strictly sequential loop
-    // (gf.py:93-100, gf.cpp:152-164) iff every firing edge (i,j) at position t sees either ALL of j's updates of this sweep
-    // (j's last firing edge is before t, and j was first visited before i) or NONE (j's first firing edge is after t) --
-    // always true when a source's edges are contiguous (graph.edges(), saveGraphToEdgeListTxt), and for many interleaved
-    // lists too.  A list that needs an intermediate version of a row (e.g. (1,2),(0,1),(1,3): row 0 must see X_1 between its
-    // two updates) has no schedule with two table versions; it is rejected instead of silently reordered.
-    std::vector<int64_t> first_t(n, -1), last_t(n, -1);
-    for (int64_t e = 0; e < m; ++e) {
-        const int32_t i = src[e], j = dst[e];
-        GEMHIP_REQUIRE(i >= 0 && i < n && j >= 0 && j < n, "gf_plan_create: edge %lld = (%d,%d) outside [0,%lld)", (long long)e, i, j,
-                       (long long)n);
-        if (j <= i) continue;                        // does not fire (gf.py:95, gf.cpp:157)
-        if (first_t[i] < 0) first_t[i] = e;
-        last_t[i] = e;
+// a planner's refusal in words
+static int gf_plan_refused(const char *who, const GfPlanError &err, int64_t n, const int32_t *src, const int32_t *dst)
+{
+    const long long e = (long long)err.edge;
+    switch (err.kind) {
+    case GfPlanError::EDGE_OUT_OF_RANGE:
+        return fail(GEMHIP_E_INVALID, "%s: edge %lld = (%d,%d) outside [0,%lld)", who, e, src[err.edge], dst[err.edge], (long long)n);
+    case GfPlanError::PARTLY_UPDATED:
+        return fail(GEMHIP_E_INVALID, "%s: edge %lld = (%d,%d) reads row %d while that row is only partly updated in file order "
+                    "(its firing edges span positions %lld..%lld); the sequential semantics of gf.cpp need the edges of a source "
+                    "to be contiguous (graph.edges() order) -- group the list by source first if the reordering is acceptable",
+                    who, e, src[err.edge], dst[err.edge], dst[err.edge], (long long)err.first, (long long)err.last);
+    case GfPlanError::TOO_MANY_UNITS: return fail(GEMHIP_E_INVALID, "%s: more than 2^31 - 1 units", who);
+    default: return GEMHIP_OK;
     }
-    for (int64_t e = 0; e < m; ++e) {
-        const int32_t i = src[e], j = dst[e];
-        if (j <= i || first_t[j] < 0) continue;      // j never fires: its row is the same in both tables
-        const bool ok = first_t[j] < first_t[i] ? last_t[j] < e : first_t[j] > e;
-        GEMHIP_REQUIRE(ok, "gf_plan_create: edge %lld = (%d,%d) reads row %d while that row is only partly updated in file order "
-                       "(its firing edges span positions %lld..%lld); the sequential semantics of gf.cpp need the edges of a source "
-                       "to be contiguous (graph.edges() order) -- group the list by source first if the reordering is acceptable",
-                       (long long)e, i, j, j, (long long)first_t[j], (long long)last_t[j]);
-    }
-    for (int64_t e = 0; e < m; ++e) {
-        const int32_t i = src[e], j = dst[e];
-        if (j <= i || i < row_begin || i >= row_end) continue;
-        if (pos[i] < 0) { pos[i] = (int32_t)order.size(); order.push_back(i); deg.push_back(0); }
-        ++deg[pos[i]];
-    }
-    const int64_t nrows = (int64_t)order.size();
-    std::vector<int64_t> off(nrows + 1, 0);
-    for (int64_t r = 0; r < nrows; ++r) off[r + 1] = off[r] + deg[r];
-    const int64_t nupd = off[nrows];
-    std::vector<uint32_t> col(nupd);
-    std::vector<float> wt(nupd);
-    {
-        std::vector<int64_t> fill(off.begin(), off.end() - 1);
-        for (int64_t e = 0; e < m; ++e) {
-            const int32_t i = src[e], j = dst[e];
-            if (j <= i || i < row_begin || i >= row_end) continue;
-            const int64_t q = fill[pos[i]]++;
-            col[q] = (uint32_t)j;
-            wt[q] = w ? w[e] : 1.0f;
-        }
-    }
-    // 2. levels: row i must run after every neighbour j (j>i) that the reference visits earlier.
-    std::vector<int32_t> level(nrows, 0);
-    int32_t nlevels = nrows ? 1 : 0;
-    for (int64_t r = 0; r < nrows; ++r) {
-        int32_t lv = 0;
-        for (int64_t q = off[r]; q < off[r + 1]; ++q) {
-            const int32_t pj = pos[col[q]];
-            if (pj >= 0 && pj < r) {          // j already updated in this sweep -> read X_new[j]
-                col[q] |= 0x80000000u;
-                lv = std::max(lv, level[pj] + 1);
-            }
-        }
-        level[r] = lv;
-        nlevels = std::max(nlevels, lv + 1);
-    }
-    // 3. stable sort rows by level
-    std::vector<int64_t> lvl_cnt(nlevels + 1, 0);
-    for (int64_t r = 0; r < nrows; ++r) ++lvl_cnt[level[r] + 1];
-    for (int32_t l = 0; l < nlevels; ++l) lvl_cnt[l + 1] += lvl_cnt[l];
-    std::vector<int64_t> level_hubs;
-    std::vector<int32_t> rows_sorted(nrows);
-    std::vector<int64_t> ptr_sorted(nrows + 1, 0);
-    std::vector<uint32_t> col_sorted(nupd);
-    std::vector<float> w_sorted(nupd);
-    {
-        // inside a level the rows are independent: hub rows (gf_hub_kernel) first, the others keep the reference's visiting order
-        std::vector<int64_t> at(lvl_cnt.begin(), lvl_cnt.end() - 1);
-        std::vector<int64_t> newpos(nrows);
-        level_hubs.assign(nlevels, 0);
-        const bool hubs_on = getenv("GEMHIP_GF_NO_HUB_KERNEL") == nullptr;
-        const int64_t hub_t = getenv("GEMHIP_GF_HUB_EDGES") ? std::max(1, atoi(getenv("GEMHIP_GF_HUB_EDGES"))) : GF_HUB_EDGES;   // (tests lower it)
-        for (int64_t r = 0; r < nrows; ++r) if (hubs_on && off[r + 1] - off[r] >= hub_t) { newpos[r] = at[level[r]]++; ++level_hubs[level[r]]; }
-        for (int64_t r = 0; r < nrows; ++r) if (!(hubs_on && off[r + 1] - off[r] >= hub_t)) newpos[r] = at[level[r]]++;
-        std::vector<int64_t> inv(nrows);
-        for (int64_t r = 0; r < nrows; ++r) inv[newpos[r]] = r;
-        for (int64_t s = 0; s < nrows; ++s) {
-            const int64_t r = inv[s];
-            rows_sorted[s] = order[r];
-            ptr_sorted[s + 1] = ptr_sorted[s] + (off[r + 1] - off[r]);
-            std::copy(col.begin() + off[r], col.begin() + off[r + 1], col_sorted.begin() + ptr_sorted[s]);
-            std::copy(wt.begin() + off[r], wt.begin() + off[r + 1], w_sorted.begin() + ptr_sorted[s]);
-        }
-    }
+}
 
+// the host plan H (planned since t_host0) becomes a device plan: H's small vectors move into it, its arrays are uploaded
+static int gf_plan_upload(const char *who, int64_t n, int32_t d, GfHostPlan &H, double t_host0, gemhip_gf_plan_t *out)
+{
     auto *p = new gemhip_gf_plan();
-    p->n = n; p->d = d; p->nrows = nrows; p->nupd = nupd;
-    p->level_off.assign(lvl_cnt.begin(), lvl_cnt.end());
-    p->level_hubs = level_hubs;
-    p->level_maxlen.assign(nlevels, 0);
-    for (int32_t l = 0; l < nlevels; ++l)
-        for (int64_t q = lvl_cnt[l] + level_hubs[l]; q < lvl_cnt[l + 1]; ++q) p->level_maxlen[l] = std::max(p->level_maxlen[l], ptr_sorted[q + 1] - ptr_sorted[q]);
-    if (hipGetDevice(&p->device) != hipSuccess) { delete p; return fail(GEMHIP_E_HIP, "gf_plan_create: no HIP device"); }
+    p->n = n; p->d = d; p->fn = gf_launchers_for(d);
+    p->nrows = H.nrows; p->nupd = H.nupd; p->units = H.units;
+    p->level_off.swap(H.level_off); p->level_hubs.swap(H.level_hubs); p->level_maxlen.swap(H.level_maxlen); p->segs.swap(H.segs);
+    if (hipGetDevice(&p->device) != hipSuccess) { delete p; return fail(GEMHIP_E_HIP, "%s: no HIP device", who); }
     phase_acc()[PH_HOST] += phase_now() - t_host0;
     PhaseScope ph_up(PH_H2D);
-    hipError_t e = p->d_rows.upload(rows_sorted.data(), nrows);
-    if (e == hipSuccess) e = p->d_ptr.upload(ptr_sorted.data(), nrows + 1);
-    if (e == hipSuccess) e = p->d_col.upload(col_sorted.data(), nupd);
-    if (e == hipSuccess) e = p->d_w.upload(w_sorted.data(), nupd);
+    hipError_t e = p->d_rows.upload(H.rows.data(), H.nrows);
+    if (e == hipSuccess) e = p->d_ptr.upload(H.ptr.data(), H.nrows + 1);
+    if (e == hipSuccess) e = p->d_col.upload(H.col.data(), H.nupd);
+    if (e == hipSuccess) e = p->d_w.upload(H.w.data(), H.nupd);
+    if (e == hipSuccess && H.units) e = p->d_level_off.upload(p->level_off.data(), p->level_off.size());
     if (e != hipSuccess) {
         gemhip_gf_plan_destroy(p);
-        return fail(GEMHIP_E_HIP, "gf_plan_create: device upload failed: %s", hipGetErrorString(e));
+        return fail(GEMHIP_E_HIP, "%s: device upload failed: %s", who, hipGetErrorString(e));
     }
     *out = p;
     return GEMHIP_OK;
+}
+
+extern "C" int gemhip_gf_plan_create(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, const float *w, int32_t d,
+                                     int64_t row_begin, int64_t row_end, gemhip_gf_plan_t *out)
+{
+    const char *who = "gf_plan_create";
+    if (int rc = gf_validate(who, n, m, src, dst, out)) return rc;
+    GEMHIP_REQUIRE(d >= 1, "gf_plan_create: d=%d", d);
+    GEMHIP_REQUIRE(gf_launchers_for(d) != nullptr, "gf_plan_create: d=%d unsupported (even d <= 1024, odd d <= 512)", d);
+    GEMHIP_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= n, "gf_plan_create: bad row range");
+    const double t_host0 = phase_now();
+    // rows with at least this many firing edges get a workgroup (gf_hub_kernel); 0: none do.  Read per call (tests lower it)
+    const int64_t hub_edges = getenv("GEMHIP_GF_NO_HUB_KERNEL") ? 0 : getenv("GEMHIP_GF_HUB_EDGES") ? std::max(1, atoi(getenv("GEMHIP_GF_HUB_EDGES"))) : GF_HUB_EDGES;
+    GfHostPlan H;
+    // a list that needs an intermediate version of a row is rejected instead of silently reordered
+    if (const GfPlanError err = gf_plan_rows(n, m, src, dst, w, row_begin, row_end, hub_edges, H)) return gf_plan_refused(who, err, n, src, dst);
+    return gf_plan_upload(who, n, d, H, t_host0, out);
 }
 
 extern "C" int gemhip_gf_any_order_schedule(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, int32_t *unit_out, int32_t *level_out,
@@ -887,8 +693,8 @@ extern "C" int gemhip_gf_any_order_schedule(int64_t n, int64_t m, const int32_t 
 {
     GEMHIP_REQUIRE(n > 0 && n < (int64_t)0x7fffffff, "gf_any_order_schedule: n=%lld out of range", (long long)n);
     GEMHIP_REQUIRE(m >= 0 && (m == 0 || (src && dst)), "gf_any_order_schedule: bad edge arrays");
-    gf_unit_schedule S;
-    if (int rc = gf_schedule_units("gf_any_order_schedule", n, m, src, dst, S)) return rc;
+    GfUnitSchedule S;
+    if (const GfPlanError err = gf_schedule_units(n, m, src, dst, S)) return gf_plan_refused("gf_any_order_schedule", err, n, src, dst);
     for (int64_t e = 0; e < m; ++e) {
         const int32_t u = S.unit_of[e];
         if (unit_out) unit_out[e] = u;
@@ -899,76 +705,26 @@ extern "C" int gemhip_gf_any_order_schedule(int64_t n, int64_t m, const int32_t 
     return GEMHIP_OK;
 }
 
-constexpr int GF_FUSED_LEVELS_DEFAULT = 16;
-
 extern "C" int gemhip_gf_plan_create_any_order(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, const float *w, int32_t d,
                                                int32_t flags, gemhip_gf_plan_t *out)
 {
-    GEMHIP_REQUIRE(out != nullptr, "gf_plan_create_any_order: out is NULL");
-    *out = nullptr;
-    GEMHIP_REQUIRE(n > 0 && n < (int64_t)0x7fffffff, "gf_plan_create_any_order: n=%lld out of range", (long long)n);
-    GEMHIP_REQUIRE(m >= 0 && (m == 0 || (src && dst)), "gf_plan_create_any_order: bad edge arrays");
-    GEMHIP_REQUIRE(d >= 1 && pick_sweep(d) != nullptr, "gf_plan_create_any_order: d=%d unsupported (even d <= 1024, odd d <= 512)", d);
+    const char *who = "gf_plan_create_any_order";
+    if (int rc = gf_validate(who, n, m, src, dst, out)) return rc;
+    GEMHIP_REQUIRE(gf_launchers_for(d) != nullptr, "gf_plan_create_any_order: d=%d unsupported (even d <= 1024, odd d <= 512)", d);
     GEMHIP_REQUIRE((flags & ~1) == 0, "gf_plan_create_any_order: flags=%d (bit 0 = force the unit schedule)", flags);
-    // a list the row schedule represents gets exactly that plan: same levels, same kernels, same speed
-    if (!(flags & 1) && gf_rows_schedule_represents(n, m, src, dst)) return gemhip_gf_plan_create(n, m, src, dst, w, d, 0, n, out);
-
+    // a list the row schedule represents gets exactly that plan: same levels, same kernels, same speed (and one with an endpoint out of range
+    // goes there too: that call reports it)
+    if (!(flags & 1) && gf_check_row_order(n, m, src, dst).kind != GfPlanError::PARTLY_UPDATED) return gemhip_gf_plan_create(n, m, src, dst, w, d, 0, n, out);
     const double t_host0 = phase_now();
-    gf_unit_schedule S;
-    if (int rc = gf_schedule_units("gf_plan_create_any_order", n, m, src, dst, S)) return rc;
-    // units sorted by level (inside a level: creation order), each unit's edges in file order
-    const int64_t nunits = (int64_t)S.row.size();
-    std::vector<int64_t> level_off(S.nlevels + 1, 0);
-    for (int64_t u = 0; u < nunits; ++u) ++level_off[S.level[u] + 1];
-    for (int32_t l = 0; l < S.nlevels; ++l) level_off[l + 1] += level_off[l];
-    std::vector<int64_t> slot(nunits), ptr(nunits + 1, 0);
-    std::vector<int32_t> units(nunits);
-    {
-        std::vector<int64_t> at(level_off.begin(), level_off.end() - 1);
-        for (int64_t u = 0; u < nunits; ++u) {
-            slot[u] = at[S.level[u]]++;
-            units[slot[u]] = (int32_t)((uint32_t)S.row[u] | (S.own_new[u] ? 0x80000000u : 0u));
-        }
-    }
-    for (int64_t e = 0; e < m; ++e) if (S.unit_of[e] >= 0) ++ptr[slot[S.unit_of[e]] + 1];
-    for (int64_t u = 0; u < nunits; ++u) ptr[u + 1] += ptr[u];
-    std::vector<uint32_t> col(S.nupd);
-    std::vector<float> wt(S.nupd);
-    {
-        std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
-        for (int64_t e = 0; e < m; ++e) {
-            if (S.unit_of[e] < 0) continue;
-            const int64_t q = fill[slot[S.unit_of[e]]]++;
-            col[q] = (uint32_t)dst[e] | (S.nb_new[e] ? 0x80000000u : 0u);
-            wt[q] = w ? w[e] : 1.0f;
-        }
-    }
-    auto *p = new gemhip_gf_plan();
-    p->n = n; p->d = d; p->nrows = nunits; p->nupd = S.nupd; p->units = true;
-    p->level_off = level_off;
-    p->fused_levels = GF_FUSED_LEVELS_DEFAULT;
-    gf_units_segments(p);
-    if (hipGetDevice(&p->device) != hipSuccess) { delete p; return fail(GEMHIP_E_HIP, "gf_plan_create_any_order: no HIP device"); }
-    phase_acc()[PH_HOST] += phase_now() - t_host0;
-    PhaseScope ph_up(PH_H2D);
-    hipError_t e = p->d_rows.upload(units.data(), nunits);
-    if (e == hipSuccess) e = p->d_ptr.upload(ptr.data(), nunits + 1);
-    if (e == hipSuccess) e = p->d_col.upload(col.data(), S.nupd);
-    if (e == hipSuccess) e = p->d_w.upload(wt.data(), S.nupd);
-    if (e == hipSuccess) e = p->d_level_off.upload(level_off.data(), level_off.size());
-    if (e != hipSuccess) {
-        gemhip_gf_plan_destroy(p);
-        return fail(GEMHIP_E_HIP, "gf_plan_create_any_order: device upload failed: %s", hipGetErrorString(e));
-    }
-    *out = p;
-    return GEMHIP_OK;
+    GfHostPlan H;
+    if (const GfPlanError err = gf_plan_units(n, m, src, dst, w, GF_FUSED_LEVELS_DEFAULT, H)) return gf_plan_refused(who, err, n, src, dst);
+    return gf_plan_upload(who, n, d, H, t_host0, out);
 }
 
 extern "C" int gemhip_gf_plan_set_fused_levels(gemhip_gf_plan_t p, int32_t max_units)
 {
     GEMHIP_REQUIRE(p && max_units >= 0 && max_units <= GF_FUSED_WAVES, "gf_plan_set_fused_levels: 0 (off) .. %d units", GF_FUSED_WAVES);
-    p->fused_levels = max_units;
-    if (p->units) gf_units_segments(p);
+    if (p->units) p->segs = gf_units_segments(p->level_off, max_units);
     return GEMHIP_OK;
 }
 
@@ -1028,27 +784,25 @@ extern "C" int gemhip_gf_plan_sweeps(gemhip_gf_plan_t p, int32_t nsweeps, float 
     if (p->nrows == 0) return GEMHIP_OK;
     hipStream_t s = (hipStream_t)stream;
     if (p->units) {                                    // unit schedule: the launches of gf_units_segments, in stream order
-        const units_fns uf = pick_units((int)p->d);
         for (int it = 0; it < nsweeps; ++it) {
             const float *Xold = p->X[p->cur];
             float *Xnew = p->X[p->cur ^ 1];
             for (const auto &g : p->segs) {
-                if (g.fused) uf.fused(p, g.l0, g.l1, Xold, Xnew, eta, regu, s);
-                else uf.level(p, p->level_off[g.l0], p->level_off[g.l1] - p->level_off[g.l0], Xold, Xnew, eta, regu, s);
+                if (g.fused) p->fn->units_fused(p, g.l0, g.l1, Xold, Xnew, eta, regu, s);
+                else p->fn->units(p, p->level_off[g.l0], p->level_off[g.l1] - p->level_off[g.l0], Xold, Xnew, eta, regu, s);
             }
             p->cur ^= 1;
         }
         GEMHIP_CHECK(hipGetLastError());
         return GEMHIP_OK;
     }
-    const sweep_fn fn = pick_sweep((int)p->d);
     const int nlevels = (int)p->level_off.size() - 1;
     int it0 = 0;
-    if (p->fused_sweeps > 1 && nlevels == 1 && (p->level_hubs.empty() || p->level_hubs[0] == 0) && pick_coop((int)p->d)) {
+    if (p->fused_sweeps > 1 && nlevels == 1 && (p->level_hubs.empty() || p->level_hubs[0] == 0)) {
         // up to fused_sweeps sweeps per cooperative launch; the table of sweep k is X[cur ^ (k & 1)]
         while (nsweeps - it0 >= 2) {
             const int k = std::min(nsweeps - it0, p->fused_sweeps);
-            if (int rc = pick_coop((int)p->d)(p, p->X[p->cur], p->X[p->cur ^ 1], eta, regu, k, s)) return rc;
+            if (int rc = p->fn->coop(p, p->X[p->cur], p->X[p->cur ^ 1], eta, regu, k, s)) return rc;
             if (k & 1) p->cur ^= 1;
             it0 += k;
         }
@@ -1067,10 +821,10 @@ extern "C" int gemhip_gf_plan_sweeps(gemhip_gf_plan_t p, int32_t nsweeps, float 
                 }
                 GEMHIP_CHECK(hipEventRecord(p->hub_fork, s));
                 GEMHIP_CHECK(hipStreamWaitEvent(p->hub_stream, p->hub_fork, 0));
-                pick_hub((int)p->d)(p, r0, nh, Xold, Xnew, eta, regu, p->hub_stream);
+                p->fn->hub(p, r0, nh, Xold, Xnew, eta, regu, p->hub_stream);
                 GEMHIP_CHECK(hipEventRecord(p->hub_join, p->hub_stream));
             }
-            if (nr - nh > 0) fn(p, r0 + nh, nr - nh, Xold, Xnew, eta, regu, s);
+            if (nr - nh > 0) p->fn->sweep(p, l, r0 + nh, nr - nh, Xold, Xnew, eta, regu, s);
             if (nh > 0) GEMHIP_CHECK(hipStreamWaitEvent(s, p->hub_join, 0));
         }
         p->cur ^= 1;
@@ -1115,13 +869,12 @@ extern "C" int gemhip_gf_plan_info(gemhip_gf_plan_t p, int64_t *info)
     info[0] = p->nupd; info[1] = p->nrows; info[2] = (int64_t)p->level_off.size() - 1; info[3] = p->n; info[4] = p->d;
     // 3*4d + 12 bytes per update (read X_i, read X_j, write X_i, (i,j,w))
     info[5] = p->nupd * (3 * 4 * p->d + 12);
-    {   // rows per wavefront the largest level's sweep launch will use (1: gf_sweep_kernel, > 1: gf_sweep_rows_kernel)
+    {   // rows per wavefront the largest level's sweep launch will use (1: gf_sweep_kernel, > 1: gf_sweep_rows_kernel); of equally large levels: the last
         int64_t big = 0;
-        for (size_t l = 0; l + 1 < p->level_off.size(); ++l) big = std::max<int64_t>(big, p->level_off[l + 1] - p->level_off[l]);
-        int64_t bigmax = 0;
+        size_t lbig = p->level_off.size();                       // (no level: the rule on an empty one)
         for (size_t l = 0; l + 1 < p->level_off.size(); ++l)
-            if (p->level_off[l + 1] - p->level_off[l] == big) bigmax = p->level_maxlen.size() > l ? p->level_maxlen[l] : 0;
-        info[6] = p->units ? 1 : p->rows_per_wave > 0 ? p->rows_per_wave : (bigmax > 2 * WAVE ? 1 : gf_rows_per_wave(big));
+            if (p->level_off[l + 1] - p->level_off[l] >= big) { big = p->level_off[l + 1] - p->level_off[l]; lbig = l; }
+        info[6] = p->units ? 1 : gf_rows_per_wave(p, lbig, big);
     }
     info[7] = p->units ? 1 : 0;
     return GEMHIP_OK;

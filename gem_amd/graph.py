@@ -209,7 +209,7 @@ def group_edges_by_source(src, dst, w=None):
 def row_schedule_represents(src, dst):
     """True when GF's row schedule (one wavefront per source row, two table copies: gemhip_gf_plan_create) can reproduce the sequential loop
     over this edge order: every firing edge (dst > src) reads a row that has had all or none of its own updates of the sweep at that point
-    of the list.  The test of gem_amd/csrc/gf.hip restated on arrays -- pure host code, so a caller can decide before any device call."""
+    of the list.  The rule of gem_amd/csrc/gf_plan.hip (gf_check_row_order) restated on arrays -- pure host code, so a caller can decide before any device call."""
     src = np.asarray(src, dtype=np.int64); dst = np.asarray(dst, dtype=np.int64)
     e = np.flatnonzero(dst > src)
     if e.size == 0:

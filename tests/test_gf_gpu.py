@@ -255,6 +255,44 @@ def test_fused_sweeps_in_one_cooperative_launch_are_bit_identical(d, k, grid, sb
         assert_close(out[k], oracle.gf_train_f32(n, src, dst, w, d, 0.02, 0.01, 14, X0))
 
 
+@pytest.mark.parametrize('d', [65, 129, 257, 514, 1024])
+def test_wide_and_odd_widths_match_the_oracle_on_every_schedule(d, karate):
+    """The instantiations no other test pins to the oracle: one float per lane with 2 / 4 / 8 chunks (d = 65, 129, 257) and two floats per lane with
+    8 chunks (d = 514, 1024).  All kernels share one row body, so kernel-against-kernel equality alone cannot catch a bug in it: every table is compared
+    with the CPU oracle (the tolerance of test_karate_matches_oracle_all_widths), and the four schedules -- one row per wavefront, two rows per
+    wavefront, two sweeps per cooperative launch, the forced unit schedule -- agree bit for bit.  karate as stored is multi-level (the cooperative
+    launch is for single-level plans: it keeps the launch loop there); the same edges sorted by source are one level and take it."""
+    n, src, dst, w, _ = edge_arrays(karate)
+    by_src = np.argsort(src, kind='stable')
+    L = _hip.lib()
+    for name, (s, t, ww) in (('karate', (src, dst, w)), ('karate_by_source', (src[by_src], dst[by_src], w[by_src]))):
+        s = _hip.as_i32(s); t = _hip.as_i32(t); ww = _hip.as_f32(ww)
+        X0 = (0.1 * np.random.RandomState(d).randn(n, d)).astype(np.float32)
+        ref = oracle.gf_train_f32(n, s, t, ww, d, 0.05, 0.01, 3, X0)
+        out = {}
+        for tag in ('rows1', 'rows2', 'fused2', 'units'):
+            plan = C.c_void_p()
+            edges = (n, len(s), _hip.ptr(s, C.c_int32), _hip.ptr(t, C.c_int32), _hip.ptr(ww, C.c_float), d)
+            if tag == 'units':
+                _hip.check(L.gemhip_gf_plan_create_any_order(*edges, 1, C.byref(plan)))
+            else:
+                _hip.check(L.gemhip_gf_plan_create(*edges, 0, n, C.byref(plan)))
+                _hip.check(L.gemhip_gf_plan_set_rows_per_wave(plan, 2 if tag == 'rows2' else 1))
+                _hip.check(L.gemhip_gf_plan_set_fused_sweeps(plan, 2 if tag == 'fused2' else 0, 0))
+            info = (C.c_int64 * 8)()
+            _hip.check(L.gemhip_gf_plan_info(plan, info))
+            assert info[7] == (tag == 'units') and (info[2] == 1) == (name == 'karate_by_source')
+            _hip.check(L.gemhip_gf_plan_set_embedding(plan, _hip.ptr(X0, C.c_float)))
+            _hip.check(L.gemhip_gf_plan_sweeps(plan, 3, 0.05, 0.01, None))
+            X = np.empty_like(X0)
+            _hip.check(L.gemhip_gf_plan_get_embedding(plan, _hip.ptr(X, C.c_float)))
+            _hip.check(L.gemhip_gf_plan_destroy(plan))
+            assert_close(X, ref)
+            out[tag] = X
+        for tag in ('rows2', 'fused2', 'units'):
+            assert np.array_equal(out['rows1'], out[tag]), (name, tag)
+
+
 @pytest.mark.parametrize('case', ['karate', 'sbm1024'])
 def test_hip_equals_the_emb_file_the_gf_cpp_binary_wrote(case, request):
     """The reference's NATIVE path end to end: gf.cpp's binary, run deterministically (frozen clock, scripts/make_golden_gf_cpp.py), wrote
