@@ -17,11 +17,11 @@
 //   hope_gram_kernel    P = X^T Y per slab    MFMA fp32 (2 n m1 m2 flop), operands stream from L2
 //   hope_tsgemm_kernel  O = S + a X C         MFMA fp32 (2 n m b flop)
 #include "common.hpp"
+#include "hope_host.hpp"
 #include "sym_eig.hpp"
 #include <vector>
 #include <cmath>
 #include <algorithm>
-#include <cstring>
 #include <chrono>
 #include <cstdlib>
 
@@ -695,69 +695,35 @@ void randn(Hope &H, float *X, int b, int ld, uint64_t seed)
     hipLaunchKernelGGL(hope_randn_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, H.s, X, H.n, b, ld, seed);
 }
 
-// Upper-triangular Cholesky G = R^T R in fp64 with a pivot floor; on success C = R^-1 (so that (Y C)^T (Y C) = I).
-// Returns false when a pivot falls below the floor (rank deficient or ill conditioned block): the caller then
-// takes the rank-revealing eigen path.
-bool chol_inverse(int b, const std::vector<double> &G, double floor, std::vector<double> &C)
+// The device half of orth() / orth_scaled(): per pass the Gram matrix of the block's columns comes in, host_pass(keep, G, C) turns it into the
+// keep x nk coefficients, and Y <- Y C goes out through Tmp.  Returns the number of columns kept.
+template <typename HostPass>
+int orth_passes(Hope &H, float *Y, int ld, int b, float *Tmp, int ldt, int passes, HostPass host_pass)
 {
-    std::vector<double> R((size_t)b * b, 0.0);
-    for (int j = 0; j < b; ++j) {
-        double djj = G[(size_t)j * b + j];
-        for (int k = 0; k < j; ++k) djj -= R[(size_t)k * b + j] * R[(size_t)k * b + j];
-        if (!(djj > floor)) return false;
-        const double rjj = std::sqrt(djj);
-        R[(size_t)j * b + j] = rjj;
-        for (int i = j + 1; i < b; ++i) {
-            double v = G[(size_t)j * b + i];
-            for (int k = 0; k < j; ++k) v -= R[(size_t)k * b + j] * R[(size_t)k * b + i];
-            R[(size_t)j * b + i] = v / rjj;
-        }
+    int keep = b;
+    for (int pass = 0; pass < passes && keep > 0 && !H.err; ++pass) {
+        std::vector<double> G, C;
+        gram(H, Y, ld, keep, Y, ld, keep, G);
+        if (H.err) return 0;
+        const int nk = host_pass(keep, G, C);
+        if (nk == 0) return 0;
+        tsgemm(H, Y, ld, keep, C, nk, 1.0f, nullptr, 0, Tmp, ldt);
+        HOPE_TRY(H, hipMemcpy2DAsync(Y, (size_t)ld * sizeof(float), Tmp, (size_t)ldt * sizeof(float), (size_t)nk * sizeof(float), H.n, hipMemcpyDeviceToDevice, H.s));
+        keep = nk;
     }
-    C.assign((size_t)b * b, 0.0);                           // back substitution: R C = I, C upper triangular
-    for (int j = 0; j < b; ++j) {
-        C[(size_t)j * b + j] = 1.0 / R[(size_t)j * b + j];
-        for (int i = j - 1; i >= 0; --i) {
-            double v = 0.0;
-            for (int k = i + 1; k <= j; ++k) v += R[(size_t)i * b + k] * C[(size_t)k * b + j];
-            C[(size_t)i * b + j] = -v / R[(size_t)i * b + i];
-        }
-    }
-    return true;
+    return keep;
 }
 
 // Orthonormalise the b columns of Y (n x b, ld) in place (Tmp = scratch).  Well-conditioned blocks take a
 // CholeskyQR step (Y <- Y R^-1); otherwise the Gram eigen-decomposition Y <- Y W L^-1/2 drops directions whose
-// relative energy is below `tol` or whose absolute energy is below `abs_floor` (rank revealing).  Two passes.
-// Returns the number of columns kept.
+// relative energy is below `tol` or whose absolute energy is below `abs_floor` (rank revealing: orth_pass).  Two passes.
 int orth(Hope &H, float *Y, int ld, int b, float *Tmp, int ldt, double tol, double abs_floor = 0.0, int passes = 2, bool *remixed = nullptr)
 {
-    int keep = b;
-    for (int pass = 0; pass < passes && keep > 0 && !H.err; ++pass) {
-        std::vector<double> G, w, C;
-        gram(H, Y, ld, keep, Y, ld, keep, G);
-        if (H.err) return 0;
-        double dmax = 0.0;
-        for (int i = 0; i < keep; ++i) dmax = std::max(dmax, G[(size_t)i * keep + i]);
-        int nk = keep;
-        // Cholesky pivots are Schur complements: a pivot below 1e-4 * dmax means condition > ~1e4 (or rank loss)
-        if (!chol_inverse(keep, G, std::max(1e-4 * dmax, abs_floor), C)) {
-            sym_eig(keep, G, w);                                  // ascending; G columns = eigenvectors
-            if (remixed) *remixed = true;                         // columns are no longer (triangular) images of the input columns
-            const double lmax = std::max(w[keep - 1], 0.0);
-            int first = 0;
-            while (first < keep && !(w[first] > tol * lmax && w[first] > abs_floor && w[first] > 0.0)) ++first;
-            nk = keep - first;
-            if (nk == 0) return 0;
-            C.assign((size_t)keep * nk, 0.0);
-            for (int i = 0; i < keep; ++i)
-                for (int j = 0; j < nk; ++j) C[(size_t)i * nk + j] = G[(size_t)i * keep + (keep - 1 - j)] / std::sqrt(w[keep - 1 - j]);
-        }
-        tsgemm(H, Y, ld, keep, C, nk, 1.0f, nullptr, 0, Tmp, ldt);
-        HOPE_TRY(H, hipMemcpy2DAsync(Y, (size_t)ld * sizeof(float), Tmp, (size_t)ldt * sizeof(float), (size_t)nk * sizeof(float), H.n, hipMemcpyDeviceToDevice, H.s));
-        keep = nk;
+    return orth_passes(H, Y, ld, b, Tmp, ldt, passes, [&](int keep, std::vector<double> &G, std::vector<double> &C) {
+        const int nk = orth_pass(keep, G, tol, abs_floor, C, remixed);
         tol = 1e-12; abs_floor = 0.0;                          // second pass only polishes
-    }
-    return keep;
+        return nk;
+    });
 }
 
 // Z = S X  (X: n x b):  W0 = beta A X ; Z <- W0 + beta A Z, `terms` times  => sum_{t=1..terms+1} (beta A)^t X.
@@ -853,12 +819,9 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
                       int terms, double br, int out_mode, float *U_sqrtS, float *V_sqrtS, float *sigma, double *stats)
 {
     const int b = (int)std::min<int64_t>((int64_t)k + oversample, n);
-    // basis capacity: (krylov_steps + 1) blocks for the first cycles, 20 % more for the deeper polynomial of the locked phase
-    // (fewer cycles and SpMMs against a dearer projected eigenproblem: measured optimum, scripts/hope_basis_sweep.sh)
-    int64_t basis_cols = (int64_t)b * (krylov_steps + 1);
-    basis_cols += basis_cols / 5;
-    if (const char *e = getenv("GEMHIP_HOPE_BASIS_COLS")) basis_cols = std::max<int64_t>((int64_t)b * (krylov_steps + 1), atoi(e));
-    const int mmax = (int)std::min<int64_t>(std::min<int64_t>(basis_cols, n), 512);
+    auto env_int = [](const char *name, int &v) -> const int * { const char *e = getenv(name); if (!e) return nullptr; v = atoi(e); return &v; };
+    int basis_env = 0, depth_env = 0;
+    const int mmax = krylov_basis_capacity(b, krylov_steps, n, env_int("GEMHIP_HOPE_BASIS_COLS", basis_env));
     GEMHIP_REQUIRE(b <= 512 && k <= mmax, "hope: k + oversample = %d too large (max 512)", b);
     const int ldm = (mmax + 31) / 32 * 32, ldb = (b + 31) / 32 * 32;
     DevBuf<float> Vall, Ball, T0, T1, W0, Tmp;
@@ -874,27 +837,21 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
     // Locking (deflation): a leading Ritz pair of the restart block whose residual ||S^T S v - sigma^2 v|| / sigma^2 fell
     // below lock_tol is frozen -- columns [0, nl) of Vall / Ball hold the locked right vectors and S v.  Later cycles only
     // orthogonalise against them: the Krylov blocks, the S applications and the projected eigenproblem shrink with every
-    // lock.  (|sigma error| / sigma ~ residual^2 * sigma^2 / gap, so sqrt(tol)/10 keeps locked values inside `tol`.)
+    // lock.
     std::vector<double> sig_old(k, 0.0), sig(k, 0.0), Wv, ev, Zt, lock_sig, act_sig;   // ev: Ritz values DESCENDING, Zt: their vectors (column-major ma x mt)
     int mt = 0;
     int mc = 0, restarts_done = 0, nl = 0, ma = 0;
     bool v0_is_ritz = false;
     const bool locking = getenv("GEMHIP_HOPE_NO_LOCK") == nullptr;
-    const double lock_tol = 0.1 * std::sqrt(std::max((double)tol, 1e-12));
-    const int b_min = std::min(b, std::max(2 * (int)oversample, 16));
+    const double lock_tol = lock_tolerance(tol);
+    const int b_min = krylov_b_min(b, oversample);
     double last_change = 1.0, last_residual = 1.0;
     bool exact = false;
     const bool debug = getenv("GEMHIP_HOPE_DEBUG") != nullptr;
     for (int rs = 0; rs <= max_restarts && !H.err; ++rs) {
         mc = nl + m0;
         int prev_off = nl, prev_b = m0, b_valid = nl;               // Ball columns [0, b_valid) hold S Vall
-        // the basis budget (mmax columns) that locked pairs no longer need buys a deeper Krylov polynomial for the rest
-        int steps = krylov_steps;
-        if (nl > 0 && m0 > 0 && getenv("GEMHIP_HOPE_FIXED_DEPTH") == nullptr) {
-            int cols = mmax;
-            if (const char *e = getenv("GEMHIP_HOPE_DEPTH_COLS")) cols = std::min(mmax, std::max(atoi(e), nl + m0));
-            steps = std::max(steps, (cols - nl) / m0 - 1);
-        }
+        const int steps = getenv("GEMHIP_HOPE_FIXED_DEPTH") ? krylov_steps : krylov_steps_after_lock(krylov_steps, mmax, nl, m0, env_int("GEMHIP_HOPE_DEPTH_COLS", depth_env));
         for (int j = 1; j <= steps && mc < mmax && !H.err; ++j) {
             // W = S^T S V_{j-1};  S V_{j-1} is also the block of B = S Vall the Rayleigh-Ritz step needs: keep it in place
             apply_S(H, Vall + prev_off, ldm, prev_b, terms, T0, T1, W0, ldb, Ball + prev_off, ldm);
@@ -932,10 +889,7 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
                 const int want = k - nl;                            // wanted pairs still active (the leading ones of V_0)
                 for (int c = 0; c < std::min(want, prev_b) && !H.err; ++c) r2 = std::max(r2, D[(size_t)c * prev_b + c]);
                 last_residual = std::sqrt(r2) / (sig_old[0] * sig_old[0]);
-                int newl = 0;
-                if (locking && v0_is_ritz && !H.err)
-                    while (newl < want - 1 && newl < prev_b - b_min && act_sig[newl] > 0 &&
-                           std::sqrt(std::max(D[(size_t)newl * prev_b + newl], 0.0)) < lock_tol * act_sig[newl] * act_sig[newl]) ++newl;
+                const int newl = locking && v0_is_ritz && !H.err ? krylov_lock_count(want, prev_b, b_min, act_sig, D, lock_tol) : 0;
                 if (newl > 0) {
                     // columns [nl, nl+newl) of Vall / Ball already are v_c and S v_c: freezing them is a change of bookkeeping
                     for (int c = 0; c < newl; ++c) lock_sig.push_back(act_sig[c]);
@@ -965,26 +919,17 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
         mt = std::min(ma, b);                                       // restart block and output never use more than b Ritz pairs
         sym_eig_top(ma, Wv, mt, ev, Zt);
         GEMHIP_REQUIRE(mc >= k, "hope: Krylov space collapsed to %d < k=%d columns (rank-deficient S?)", mc, k);
-        {
-            std::vector<double> all(lock_sig);
-            for (int j = 0; j < std::min(mt, k); ++j) all.push_back(std::sqrt(std::max(ev[j], 0.0)));
-            std::sort(all.begin(), all.end(), std::greater<double>());
-            for (int j = 0; j < k; ++j) sig[j] = all[j];                                           // descending
-        }
-        double change = 0.0;
-        for (int j = 0; j < k; ++j) change = std::max(change, std::fabs(sig[j] - sig_old[j]));
-        last_change = sig[0] > 0 ? change / sig[0] : 0.0;
-        sig_old = sig;
+        std::vector<double> all(lock_sig);
+        for (int j = 0; j < std::min(mt, k); ++j) all.push_back(std::sqrt(std::max(ev[j], 0.0)));
+        last_change = wanted_values(all, k, sig, sig_old);                                          // sig descending
         restarts_done = rs;
         if (debug) fprintf(stderr, "[hope] cycle %d basis %d (%d locked) sigma_k %.6g sigma_1 %.6g change %.3e residual(prev cycle) %.3e\n", rs, mc, nl, sig[k - 1], sig[0], last_change, last_residual);
         exact = (mc >= n);
         const bool done = exact || (rs > 0 && last_change < tol) || rs == max_restarts;
         if (done) break;
         // restart from the best right Ritz vectors of the active part:  V0 <- Vall[:, nl:] Wv[:, top]
-        const int nb = std::min(mt, std::max(b - nl, b_min));
-        std::vector<double> C((size_t)ma * nb);
-        for (int i = 0; i < ma; ++i)
-            for (int j = 0; j < nb; ++j) C[(size_t)i * nb + j] = Zt[(size_t)j * ma + i];
+        std::vector<double> C;
+        const int nb = krylov_restart_block(mt, b, nl, b_min, ma, Zt, C);
         tsgemm(H, Vall + nl, ldm, ma, C, nb, 1.0f, nullptr, 0, Tmp, ldm);
         HOPE_TRY(H, hipMemcpy2DAsync(Vall + nl, (size_t)ldm * sizeof(float), Tmp, (size_t)ldm * sizeof(float), (size_t)nb * sizeof(float), n, hipMemcpyDeviceToDevice, H.s));
         bool remixed = false;
@@ -996,24 +941,11 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
     if (!H.err) {
         // U sqrt(S) = B W S^-1/2 ,  V sqrt(S) = Vall W S^1/2 over the locked columns (W = identity there) and the active Ritz
         // vectors; the k largest sigma, columns in ASCENDING sigma (svds order, hope.py:33)
-        struct Cand { double s; int locked; int idx; };
-        std::vector<Cand> cand;
-        for (int l = 0; l < nl; ++l) cand.push_back({lock_sig[l], 1, l});
-        for (int j = 0; j < std::min(mt, k); ++j) cand.push_back({std::sqrt(std::max(ev[j], 0.0)), 0, j});
-        std::stable_sort(cand.begin(), cand.end(), [](const Cand &x, const Cand &y) { return x.s > y.s; });
-        std::vector<double> Cu((size_t)mc * k, 0.0), Cv((size_t)mc * k, 0.0);
-        for (int r = 0; r < k; ++r) {
-            const int j = k - 1 - r;                         // output column (ascending sigma)
-            const double s = cand[r].s;
-            sigma[j] = (float)s;
-            const double su = out_mode == 1 ? (s > 0 ? 1.0 / s : 0.0) : (s > 0 ? 1.0 / std::sqrt(s) : 0.0), sv = out_mode == 1 ? 1.0 : std::sqrt(s);
-            if (cand[r].locked) { Cu[(size_t)cand[r].idx * k + j] = su; Cv[(size_t)cand[r].idx * k + j] = sv; }
-            else
-                for (int i = 0; i < ma; ++i) {
-                    const double wv = Zt[(size_t)cand[r].idx * ma + i];
-                    Cu[(size_t)(nl + i) * k + j] = wv * su; Cv[(size_t)(nl + i) * k + j] = wv * sv;
-                }
-        }
+        std::vector<OutCand> cand;
+        for (int l = 0; l < nl; ++l) cand.push_back({lock_sig[l], 1.0, l});
+        for (int j = 0; j < std::min(mt, k); ++j) cand.push_back({std::sqrt(std::max(ev[j], 0.0)), 1.0, nl + j});
+        std::vector<double> Cu, Cv;
+        select_outputs(cand, k, nl, ma, &Zt, true, out_mode == 1, sigma, Cu, Cv);
         // deterministic sign: largest-magnitude entry of each left vector positive (svds signs are arbitrary; the first such row on ties).  The
         // arg-maxima are taken on the device from the compact [n][k] product, the signs go into the coefficients and the product is formed again
         // (one more 36 us GEMM; rounds 1-2 flipped the n x k outputs in two host passes -- ~10 ms at 100k x 64, and impossible for device outputs)
@@ -1027,12 +959,7 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
             HOPE_TRY(H, hipMemcpyAsync(cm.data(), d_cm, (size_t)k * sizeof(float), hipMemcpyDeviceToHost, H.s));
             HOPE_TRY(H, hipStreamSynchronize(H.s));
         }
-        bool any = false;
-        for (int j = 0; j < k; ++j)
-            if (cm[j] < 0.f) {
-                any = true;
-                for (int i = 0; i < mc; ++i) { Cu[(size_t)i * k + j] = -Cu[(size_t)i * k + j]; Cv[(size_t)i * k + j] = -Cv[(size_t)i * k + j]; }
-            }
+        const bool any = flip_negative_columns(mc, k, std::vector<double>(cm.begin(), cm.end()), Cu, Cv);
         if (U_sqrtS) {
             if (any) tsgemm(H, Ball, ldm, mc, Cu, k, 1.0f, nullptr, 0, Tmp, k);
             HOPE_TRY(H, hipMemcpy(U_sqrtS, Tmp, (size_t)n * k * sizeof(float), hipMemcpyDefault /* host (gemhip_hope_plan_solve) or device (.._solve_device) destination */));
@@ -1043,10 +970,7 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
     float ms = 0.f;
     if (!H.err) { hipEventRecord(tm.ev1, H.s); hipEventSynchronize(tm.ev1); hipEventElapsedTime(&ms, tm.ev0, tm.ev1); }
     if (!H.err) spmm_time_collect(H); else H.sp_used = 0;
-    if (stats && !H.err) {
-        stats[0] = ms * 1e-3; stats[1] = H.spmm_count; stats[2] = H.spmm_cols; stats[3] = terms; stats[4] = mc; stats[5] = restarts_done;
-        stats[6] = last_change; stats[7] = br; stats[8] = eig_seconds(); stats[9] = eig_calls(); stats[10] = last_residual; stats[11] = H.spmm_ms * 1e-3;
-    }
+    if (stats && !H.err) fill_solve_stats(stats, ms, H.spmm_count, H.spmm_cols, terms, mc, restarts_done, last_change, br, last_residual, H.spmm_ms);
     return H.err;
 }
 
@@ -1063,39 +987,10 @@ static int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t
 // SpMM columns, no n x 512 basis and no 512 x 512 projected eigenproblem (measured: DESIGN.md 3.2).
 namespace {
 
-// CholeskyQR on the column-NORMALISED Gram matrix (filtered columns differ in length by the filter's growth; an entry of the fp32
-// Gram matrix is accurate relative to the product of its two column norms, so the scaled matrix is accurate entrywise).  Falls back
-// to the scaled Gram's eigen-decomposition when a pivot is lost, dropping directions below 1e-6 relative energy.
+// CholeskyQR on the column-NORMALISED Gram matrix, with the scaled Gram's eigen-decomposition as the fallback (orth_scaled_pass)
 int orth_scaled(Hope &H, float *Y, int ld, int b, float *Tmp, int ldt, int passes)
 {
-    int keep = b;
-    for (int pass = 0; pass < passes && keep > 0 && !H.err; ++pass) {
-        std::vector<double> G, w, C, dinv(keep, 0.0);
-        gram(H, Y, ld, keep, Y, ld, keep, G);
-        if (H.err) return 0;
-        for (int i = 0; i < keep; ++i) { const double g = G[(size_t)i * keep + i]; dinv[i] = (g > 0.0 && std::isfinite(g)) ? 1.0 / std::sqrt(g) : 0.0; }
-        for (int i = 0; i < keep; ++i)
-            for (int j = 0; j < keep; ++j) G[(size_t)i * keep + j] *= dinv[i] * dinv[j];
-        for (int i = 0; i < keep; ++i) if (dinv[i] == 0.0) G[(size_t)i * keep + i] = 0.0;
-        int nk = keep;
-        if (!chol_inverse(keep, G, 1e-5, C)) {
-            sym_eig(keep, G, w);
-            const double lmax = std::max(w[keep - 1], 0.0);
-            int first = 0;
-            while (first < keep && !(w[first] > 1e-6 * lmax && w[first] > 0.0)) ++first;
-            nk = keep - first;
-            if (nk == 0) return 0;
-            C.assign((size_t)keep * nk, 0.0);
-            for (int i = 0; i < keep; ++i)
-                for (int j = 0; j < nk; ++j) C[(size_t)i * nk + j] = G[(size_t)i * keep + (keep - 1 - j)] / std::sqrt(w[keep - 1 - j]);
-        }
-        for (int i = 0; i < keep; ++i)
-            for (int j = 0; j < nk; ++j) C[(size_t)i * nk + j] *= dinv[i];
-        tsgemm(H, Y, ld, keep, C, nk, 1.0f, nullptr, 0, Tmp, ldt);
-        HOPE_TRY(H, hipMemcpy2DAsync(Y, (size_t)ld * sizeof(float), Tmp, (size_t)ldt * sizeof(float), (size_t)nk * sizeof(float), H.n, hipMemcpyDeviceToDevice, H.s));
-        keep = nk;
-    }
-    return keep;
+    return orth_passes(H, Y, ld, b, Tmp, ldt, passes, [](int keep, std::vector<double> &G, std::vector<double> &C) { return orth_scaled_pass(keep, G, C); });
 }
 
 // Out = Op X for the eigen-path's operators: kind 0 / 1: Op = the CSR matrix (one SpMM); kind 2 (LLE): Op = N^T N, N = I - P, through the
@@ -1154,7 +1049,7 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
     *fell_back = false;
     const auto ht0 = std::chrono::steady_clock::now();       // host timeline of the call (printed under GEMHIP_HOPE_DEBUG)
     const double beta = H.beta;
-    auto fk = [&](double x) { return kind == 1 ? 1.0 + x : kind == 2 ? beta - x : beta * x / (1.0 - beta * x); };
+    auto fk = [&](double x) { return sym_f(kind, beta, x); };
     const int b = (int)std::min<int64_t>((int64_t)k + oversample, n);
     // the SpMM kernels carry at most 512 block columns (CPL = 8) and the column-norm scratch below holds 512 floats: a wider block must be
     // refused here exactly as krylov_svd refuses it, not truncated silently
@@ -1189,36 +1084,20 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
     randn(H, Vall, b, ldv, seed);
     int ma = orth_scaled(H, Vall, ldv, b, Tmp, ldv, 1), nl = 0;      // (one CholeskyQR pass: a Gaussian block is well conditioned, and the first filter is followed by the full CholeskyQR2)
 
-    const double L = kind == 1 ? 1.0001 : kind == 2 ? beta : br / std::fabs(beta);   // |lambda| <= L: power-iteration estimate + margin
-    const double smin = kind == 2 ? 0.0 : -L, smax = L;                // the operator's spectrum lies in [smin, smax]
-    double lo = kind == 2 ? 0.25 * L : -L, hi = kind == 2 ? L : 0.5 * L, tau_prev = 0.0;      // first filter: damp the unwanted three quarters
-    const double res_floor = kind == 2 ? 0.25 * L : 0.0;              // LLE's wanted eigenvalues start at 0: residuals relative to the scale
-    const double lock_tol = 0.1 * std::sqrt(std::max((double)tol, 1e-12));
+    const SymSpectrum sp = sym_spectrum(kind, beta, br);
+    const double L = sp.L, lock_tol = lock_tolerance(tol);
+    double lo, hi, tau_prev = 0.0;
+    sym_first_interval(kind, L, lo, hi);
     const int b_min = std::min(b, (int)oversample + 2);      // the active block keeps its oversampling columns
     std::vector<double> lock_lam, th, res, sig(k, 0.0), sig_old(k, 0.0);
-    double last_change = 1.0, last_residual = 1.0, degree_total = 0.0;
+    double last_change = 1.0, last_residual = 1.0;
     int cycles = 0;
     bool converged = false;
     for (int cyc = 0; cyc < max_cycles && !H.err; ++cyc) {
         cycles = cyc + 1;
-        const double c = 0.5 * (hi + lo), e = 0.5 * (hi - lo);
-        const double tmax = std::max(smax - c, c - smin) / e;
-        const double rho = tmax + std::sqrt(std::max(tmax * tmax - 1.0, 0.0));
-        // in-filter deflation period: edge growth <= 1e6 between projections (numpy mirror, SBM 100k/1M: 1e3 / 1e4 / 1e5 / 1e6 give the
-        // same singular values with 50 / 34 / 26 / 16 projections per solve; at 1e8 the error grows tenfold.  On the device: 1e5 -> 1e6 takes a
-        // solve from 15.6 to 14.65 ms with all 64 sigma still inside the ARPACK bar, 1e7 is no faster, 1e8 fails tests/test_hope_gpu.py)
-        const int q = (int)std::max(1.0, std::floor(std::log(1e6) / std::log(std::max(rho, 1.0001))));
-        double rho_m = rho;                                       // growth that caps the degree: the spectrum's edge, or -- once pairs are
-        if (nl > 0 && cyc > 0 && !th.empty()) {                   // locked and deflated inside the filter -- the largest active Ritz value
-            double ta = 1.0;
-            for (double t : th) ta = std::max(ta, 1.02 * std::fabs(t - c) / e);
-            ta = std::min(ta, tmax);
-            rho_m = ta + std::sqrt(std::max(ta * ta - 1.0, 0.0));
-        }
-        const int m = (int)std::max(2.0, std::min((double)max_degree, std::floor(std::log(cyc == 0 ? amp0 : amp) / std::log(std::max(rho_m, 1.0001)))));
+        const SymCycle cy = sym_cycle_plan(lo, hi, sp.smin, sp.smax, th, nl, cyc, amp, amp0, max_degree);
         float *Va = Vall + nl;
-        cheb_filter(H, kind, Va, ldv, ma, m, c, e, F, ldv, Bm, Vall, ldv, nl, q);
-        degree_total += m;
+        cheb_filter(H, kind, Va, ldv, ma, cy.m, cy.c, cy.e, F, ldv, Bm, Vall, ldv, nl, cy.q);
         // CholeskyQR2 + Rayleigh-Ritz on A over the active block.  With locked vectors the projection is repeated between the two passes (the first pass
         // rescales the block).  FUSED (default; GEMHIP_HOPE_SYM_FUSED_RR=0 for the A/B): the second CholeskyQR pass is not applied to the block -- after the
         // first pass Y1 is orthonormal to ~1e-3, so G2 = Y1^T Y1 and H1 = Y1^T (A Y1) are taken in ONE host round trip (gram2), C2 = chol(G2)^-1 and
@@ -1238,35 +1117,8 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
             std::vector<double> G2;
             gram2(H, Va, ldv, keep, Va, ldv, keep, G2, Va, ldv, keep, Bm, ldv, keep, Hh);
             if (H.err) break;
-            std::vector<double> dinv(keep, 0.0);
-            for (int i = 0; i < keep; ++i) { const double g = G2[(size_t)i * keep + i]; dinv[i] = (g > 0.0 && std::isfinite(g)) ? 1.0 / std::sqrt(g) : 0.0; }
-            for (int i = 0; i < keep; ++i)
-                for (int j = 0; j < keep; ++j) G2[(size_t)i * keep + j] *= dinv[i] * dinv[j];
-            bool ok = true;
-            for (int i = 0; i < keep; ++i) if (dinv[i] == 0.0) ok = false;
-            if (ok && chol_inverse(keep, G2, 1e-5, C2)) {
-                for (int i = 0; i < keep; ++i)
-                    for (int j = 0; j < keep; ++j) C2[(size_t)i * keep + j] *= dinv[i];
-                // Hq = C2^T sym(H1) C2 (C2 upper triangular)
-                for (int i = 0; i < keep; ++i)
-                    for (int j = i + 1; j < keep; ++j) { const double v = 0.5 * (Hh[(size_t)i * keep + j] + Hh[(size_t)j * keep + i]); Hh[(size_t)i * keep + j] = Hh[(size_t)j * keep + i] = v; }
-                std::vector<double> T((size_t)keep * keep, 0.0), Hq((size_t)keep * keep, 0.0);
-                for (int i = 0; i < keep; ++i)                      // T = H1 C2
-                    for (int l = 0; l < keep; ++l) {
-                        const double h = Hh[(size_t)i * keep + l];
-                        if (h == 0.0) continue;
-                        for (int j = l; j < keep; ++j) T[(size_t)i * keep + j] += h * C2[(size_t)l * keep + j];
-                    }
-                for (int l = 0; l < keep; ++l)                      // Hq = C2^T T
-                    for (int i = l; i < keep; ++i) {
-                        const double c = C2[(size_t)l * keep + i];
-                        if (c == 0.0) continue;
-                        for (int j = 0; j < keep; ++j) Hq[(size_t)i * keep + j] += c * T[(size_t)l * keep + j];
-                    }
-                Hh.swap(Hq);
-                rr_have = true;
-            } else {
-                C2.clear();
+            if (rr_project(keep, G2, Hh, C2)) rr_have = true;
+            else {
                 keep = orth_scaled(H, Va, ldv, keep, Tmp, ldv, 1);      // (rank loss: the rank-revealing second pass, then the plain Rayleigh-Ritz step)
                 if (H.err) break;
             }
@@ -1283,30 +1135,10 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
             gram(H, Va, ldv, ma, Bm, ldv, ma, Hh);
             if (H.err) break;
         }
-        for (int i = 0; i < ma; ++i)
-            for (int j = i + 1; j < ma; ++j) { const double v = 0.5 * (Hh[(size_t)i * ma + j] + Hh[(size_t)j * ma + i]); Hh[(size_t)i * ma + j] = Hh[(size_t)j * ma + i] = v; }
+        symmetrise(ma, Hh);
         sym_eig(ma, Hh, ev);                                                          // ascending; column j of Hh = eigenvector j
-        std::vector<int> order(ma);
-        for (int j = 0; j < ma; ++j) order[j] = j;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return std::fabs(fk(ev[x])) > std::fabs(fk(ev[y])); });
-        th.assign(ma, 0.0);
-        std::vector<double> C((size_t)ma * ma), Ct((size_t)ma * ma);
-        for (int j = 0; j < ma; ++j) {
-            th[j] = ev[order[j]];
-            for (int i = 0; i < ma; ++i) C[(size_t)i * ma + j] = Hh[(size_t)i * ma + order[j]];
-        }
-        if (!C2.empty()) {                                                            // the block is Y1, not Q = Y1 C2: its coefficients are C2 W
-            std::vector<double> M((size_t)ma * ma, 0.0);
-            for (int i = 0; i < ma; ++i)
-                for (int l = i; l < ma; ++l) {
-                    const double c = C2[(size_t)i * ma + l];
-                    if (c == 0.0) continue;
-                    for (int j = 0; j < ma; ++j) M[(size_t)i * ma + j] += c * C[(size_t)l * ma + j];
-                }
-            C.swap(M);
-        }
-        for (int j = 0; j < ma; ++j)
-            for (int i = 0; i < ma; ++i) Ct[(size_t)i * ma + j] = -th[j] * C[(size_t)i * ma + j];
+        std::vector<double> C, Ct;
+        ritz_order(ma, Hh, ev, kind, beta, C2, th, C, Ct);
         // residuals R = B C - V C diag(theta), then the block becomes its Ritz vectors V C.  FUSED (default with the fused Rayleigh-Ritz step): one
         // pass computes V C and the column norms of R without storing R (ritz_rotate); otherwise three tall-skinny GEMMs and the Gram matrix of R
         res.assign(ma, 0.0);
@@ -1327,71 +1159,40 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
             for (int j = 0; j < ma; ++j) res[j] = std::sqrt(std::max(RR[(size_t)j * ma + j], 0.0));
         }
         // wanted values so far: the k largest |f| over the locked eigenvalues and the active Ritz values
-        {
-            std::vector<double> all;
-            for (double l : lock_lam) all.push_back(std::fabs(fk(l)));
-            for (int j = 0; j < ma; ++j) all.push_back(std::fabs(fk(th[j])));
-            std::sort(all.begin(), all.end(), std::greater<double>());
-            for (int j = 0; j < k; ++j) sig[j] = all[j];
-        }
-        double change = 0.0;
-        for (int j = 0; j < k; ++j) change = std::max(change, std::fabs(sig[j] - sig_old[j]));
-        last_change = sig[0] > 0 ? change / sig[0] : 0.0;
-        sig_old = sig;
+        std::vector<double> all;
+        for (double l : lock_lam) all.push_back(std::fabs(fk(l)));
+        for (int j = 0; j < ma; ++j) all.push_back(std::fabs(fk(th[j])));
+        last_change = wanted_values(all, k, sig, sig_old);
         const int want = k - nl;                                                       // wanted pairs still active: the leading ones
-        double rmax = 0.0;
-        for (int j = 0; j < std::min(want, ma); ++j) rmax = std::max(rmax, res[j] / std::max(std::max(std::fabs(th[j]), 1e-3 * L), res_floor));
-        last_residual = rmax;
+        const double rmax = last_residual = sym_residual_scale(want, th, res, L, sp.res_floor);
         if (debug)
             fprintf(stderr, "[hope-sym] cycle %d degree %d interval [%.4f, %.4f] locked %d active %d sigma_k %.6g sigma_1 %.6g change %.3e residual %.3e\n",
-                    cyc, m, lo, hi, nl, ma, sig[k - 1], sig[0], last_change, rmax);
+                    cyc, cy.m, lo, hi, nl, ma, sig[k - 1], sig[0], last_change, rmax);
         if (cyc > 0 && last_change < tol && rmax < 1e-2) { converged = true; break; }
-        int newl = 0;
-        while (newl < want - 1 && newl < ma - b_min && res[newl] < lock_tol * std::max(std::fabs(th[newl]), res_floor)) ++newl;
+        const int newl = sym_lock_count(want, b_min, th, res, lock_tol, sp.res_floor);
         if (newl > 0) {                                                                // leading columns of the active block: bookkeeping only
             for (int j = 0; j < newl; ++j) lock_lam.push_back(th[j]);
             th.erase(th.begin(), th.begin() + newl); res.erase(res.begin(), res.begin() + newl);
             nl += newl; ma -= newl;
         }
-        // next filter: bounded where |f| is below the Ritz |f| in the MIDDLE of the oversampling columns (th is sorted by |f|): the j-th
-        // Ritz |f| never exceeds the j-th true one, so no wanted value is damped, and straggling last columns cannot hold the
-        // cut-off down.  Never lowered.
-        const int want_left = k - nl;
-        const int jc = std::max(0, std::min(ma - 1, want_left + (ma - want_left) / 2 - 1));
-        const double tau = std::max(tau_prev, std::fabs(fk(th[jc])));
-        tau_prev = tau;
-        if (!(tau > 0.0)) { lo = kind == 2 ? 0.25 * L : -L; hi = kind == 2 ? L : 0.5 * L; continue; }
-        if (kind == 2) { lo = std::max(beta - tau, 0.01 * L); hi = L; }
-        else if (kind == 1) { hi = std::min(tau - 1.0, 0.98 * L); lo = -L; if (hi < -0.5 * L) hi = -0.5 * L; }
-        else {
-            hi = std::min(tau / (std::fabs(beta) * (1.0 + tau)), 0.98 * L);
-            lo = -std::min(L, tau < 1.0 ? tau / (std::fabs(beta) * (1.0 - tau)) : L);
-            if (lo > -1e-6 * L) lo = -1e-6 * L;
-        }
+        sym_next_interval(kind, beta, L, k - nl, th, tau_prev, lo, hi);
     }
     if (!H.err && !converged) { *fell_back = true; return GEMHIP_OK; }
     const auto ht2 = std::chrono::steady_clock::now();
     if (!H.err) {
-        struct Cand { double s, lam; int col; };
-        std::vector<Cand> cand;
-        for (int l = 0; l < nl; ++l) cand.push_back({std::fabs(fk(lock_lam[l])), lock_lam[l], l});
-        for (int j = 0; j < ma; ++j) cand.push_back({std::fabs(fk(th[j])), th[j], nl + j});
-        std::stable_sort(cand.begin(), cand.end(), [](const Cand &x, const Cand &y) { return x.s > y.s; });
+        std::vector<OutCand> cand;
+        for (int l = 0; l < nl; ++l) cand.push_back({std::fabs(fk(lock_lam[l])), fk(lock_lam[l]) < 0 ? -1.0 : 1.0, l});      // u = sign(f(lambda)) q
+        for (int j = 0; j < ma; ++j) cand.push_back({std::fabs(fk(th[j])), fk(th[j]) < 0 ? -1.0 : 1.0, nl + j});
         const int mc = nl + ma;
         // sign convention (largest-magnitude entry of each left vector positive) from the basis columns themselves
         colmax(H, Vall, ldv, mc, colv);
         std::vector<float> cm(mc, 0.f);
         HOPE_TRY(H, hipMemcpyAsync(cm.data(), colv, (size_t)mc * sizeof(float), hipMemcpyDeviceToHost, H.s));
         HOPE_TRY(H, hipStreamSynchronize(H.s));
-        std::vector<double> Cu((size_t)mc * k, 0.0), Cv((size_t)mc * k, 0.0);
-        for (int r = 0; r < k && !H.err; ++r) {
-            const int j = k - 1 - r;                                                   // ascending sigma (svds order, hope.py:33)
-            const double s = cand[r].s, sf = fk(cand[r].lam) < 0 ? -1.0 : 1.0;          // u = sign(f(lambda)) q
-            sigma[j] = (float)s;
-            const double flip = (sf * cm[cand[r].col] < 0) ? -1.0 : 1.0;
-            Cu[(size_t)cand[r].col * k + j] = flip * sf * std::sqrt(s);
-            Cv[(size_t)cand[r].col * k + j] = kind >= 1 ? flip : flip * std::sqrt(s);
-        }
+        std::vector<double> Cu, Cv, umax(k, 0.0);
+        select_outputs(cand, k, nl, ma, nullptr, false, kind >= 1, sigma, Cu, Cv);
+        for (int r = 0; r < k; ++r) umax[k - 1 - r] = cand[r].sgn * cm[cand[r].col];
+        flip_negative_columns(mc, k, umax, Cu, Cv);
         if (U_sqrtS) {
             tsgemm(H, Vall, ldv, mc, Cu, k, 1.0f, nullptr, 0, Tmp, k);
             HOPE_TRY(H, hipMemcpy(U_sqrtS, Tmp, (size_t)n * k * sizeof(float), hipMemcpyDefault /* host (gemhip_hope_plan_solve) or device (.._solve_device) destination */));
@@ -1410,12 +1211,8 @@ static int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t overs
         fprintf(stderr, "[hope-sym] host timeline (us): set-up %.0f | cycles %.0f | outputs %.0f | final event %.0f | spmm timers %.0f ; device window %.0f\n",
                 us(ht0, ht1), us(ht1, ht2), us(ht2, ht3), us(ht3, ht4), us(ht4, std::chrono::steady_clock::now()), ms * 1e3);
     }
-    if (stats && !H.err) {
-        stats[0] = ms * 1e-3; stats[1] = H.spmm_count; stats[2] = H.spmm_cols; stats[3] = kind >= 1 ? -(double)kind : 0.0 /* no Katz series: f on the eigenvalues (-1: the Laplacian-Eigenmaps map, -2: LLE) */; stats[4] = nl + ma;
-        stats[5] = cycles; stats[6] = last_change; stats[7] = br; stats[8] = eig_seconds(); stats[9] = eig_calls(); stats[10] = last_residual;
-        stats[11] = H.spmm_ms * 1e-3;
-    }
-    (void)degree_total;
+    if (stats && !H.err)      // stats[3]: no Katz series, f on the eigenvalues (-1: the Laplacian-Eigenmaps map, -2: LLE)
+        fill_solve_stats(stats, ms, H.spmm_count, H.spmm_cols, kind >= 1 ? -(double)kind : 0.0, nl + ma, cycles, last_change, br, last_residual, H.spmm_ms);
     return H.err;
 }
 
@@ -1426,24 +1223,12 @@ namespace {
 // runs before the entry point's first HIP call, so a bad graph is GEMHIP_E_INVALID on a machine without a GPU too.
 int check_csr(const char *who, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col)
 {
-    GEMHIP_REQUIRE(n >= 2 && nnz >= 0 && row_ptr && (nnz == 0 || col), "%s: bad CSR arguments", who);
-    GEMHIP_REQUIRE(row_ptr[0] == 0 && row_ptr[n] == nnz, "%s: row_ptr inconsistent with nnz", who);
-    for (int64_t e = 0; e < nnz; ++e) GEMHIP_REQUIRE(col[e] >= 0 && col[e] < n, "%s: column %d outside [0,%lld)", who, col[e], (long long)n);
+    int64_t e = 0;
+    const CsrError err = check_csr_arrays(n, nnz, row_ptr, col, &e);
+    GEMHIP_REQUIRE(err != CsrError::BAD_ARGUMENTS, "%s: bad CSR arguments", who);
+    GEMHIP_REQUIRE(err != CsrError::ROW_PTR, "%s: row_ptr inconsistent with nnz", who);
+    GEMHIP_REQUIRE(err != CsrError::COLUMN, "%s: column %d outside [0,%lld)", who, col[e], (long long)n);
     return GEMHIP_OK;
-}
-
-// A^T on the host by a stable counting sort: every row of A^T has its columns ascending
-struct CsrT { std::vector<int64_t> rp; std::vector<int32_t> ci; std::vector<float> va; };
-CsrT transpose_csr(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *va)
-{
-    CsrT T;
-    T.rp.assign(n + 1, 0); T.ci.resize(std::max<int64_t>(nnz, 1)); T.va.resize(std::max<int64_t>(nnz, 1));
-    for (int64_t e = 0; e < nnz; ++e) ++T.rp[col[e] + 1];
-    for (int64_t i = 0; i < n; ++i) T.rp[i + 1] += T.rp[i];
-    std::vector<int64_t> at(T.rp.begin(), T.rp.end() - 1);
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) { const int64_t q = at[col[e]]++; T.ci[q] = (int32_t)i; T.va[q] = va[e]; }
-    return T;
 }
 
 // A (values va) and, if T is given, A^T into H; returns H.err.  `who` (an entry point's message prefix, or null): first see that there is a device at all.
@@ -1519,13 +1304,6 @@ int solve_operator(Hope &H, bool symmetric, int32_t k, int32_t oversample, int32
     return krylov_svd(H, H.n, k, oversample, krylov_steps, max_restarts, tol, seed, terms, br, out_mode, U_sqrtS, V_sqrtS, sigma, stats);
 }
 
-// the solvers return their k columns by ascending sigma; Laplacian Eigenmaps and LLE hand them out the other way round
-void reverse_columns(float *V, int64_t n, int k)
-{
-    for (int64_t i = 0; i < n; ++i)
-        for (int j = 0; j < k / 2; ++j) std::swap(V[i * k + j], V[i * k + (k - 1 - j)]);
-}
-
 }  // namespace
 
 struct gemhip_hope_plan {
@@ -1545,30 +1323,7 @@ static int hope_setup(gemhip_hope_plan &P, int64_t n, int64_t nnz, const int64_t
     std::vector<float> va(std::max<int64_t>(nnz, 1));                    // values default to 1
     for (int64_t e = 0; e < nnz; ++e) { va[e] = w ? w[e] : 1.0f; P.frob2_A += (double)va[e] * (double)va[e]; }
     const CsrT T = transpose_csr(n, nnz, row_ptr, col, va.data());
-    {   // A == A^T?  Transposing A^T gives A with every row's columns ascending (stable counting sort), which is how A^T itself is
-        // stored: equal arrays => the matrices are equal (duplicates, if any, are summed by the SpMM on both sides alike).
-        bool sym = nnz > 0 && std::memcmp(T.rp.data(), row_ptr, (size_t)(n + 1) * sizeof(int64_t)) == 0;
-        if (sym) {
-            std::vector<int64_t> at(row_ptr, row_ptr + n);
-            for (int64_t j = 0; j < n && sym; ++j)
-                for (int64_t e = T.rp[j]; e < T.rp[j + 1]; ++e) {          // entry (j, i) of A^T = entry (i, j) of A: goes to row i, next free slot
-                    const int64_t i = T.ci[e], qpos = at[i]++;
-                    if (T.ci[qpos] != (int32_t)j || T.va[qpos] != T.va[e]) { sym = false; break; }
-                }
-        }
-        P.symmetric = sym;
-    }
-    // Neumann terms from a power-iteration estimate of rho(A): bound by the max absolute row/col sum too
-    double rs_max = 0.0, cs_max = 0.0;
-    {
-        std::vector<double> cs(n, 0.0);
-        for (int64_t i = 0; i < n; ++i) {
-            double rs = 0.0;
-            for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) { rs += std::fabs(va[e]); cs[col[e]] += std::fabs(va[e]); }
-            rs_max = std::max(rs_max, rs);
-        }
-        for (int64_t i = 0; i < n; ++i) cs_max = std::max(cs_max, cs[i]);
-    }
+    P.symmetric = csr_is_symmetric(n, nnz, row_ptr, T);
     if (upload_csr(H, "hope", n, nnz, row_ptr, col, va.data(), &T)) return H.err;
     // sigma_max(A) >= rho(A) by power iteration on A^T A (at most 40 steps; the 10 % margin covers what the stopping rule leaves)
     double rho = std::sqrt(power_iteration(H, 0.37, 12.9898, 40, 4, 1e-3, true, [&](float *X2, float *y) {
@@ -1576,14 +1331,12 @@ static int hope_setup(gemhip_hope_plan &P, int64_t n, int64_t nnz, const int64_t
         spmm(H, true, 1.0f, y, 1, nullptr, 0, X2 + 1, 2, 1);                         // z = A^T y
     }));
     if (H.err) return H.err;
-    rho = std::min(std::max(rho * 1.1, 1e-30), std::sqrt(rs_max * cs_max));
+    rho = std::min(std::max(rho * 1.1, 1e-30), abs_sum_bound(n, row_ptr, col, va.data()));     // the max absolute row / column sums bound it too
     const double br = std::fabs((double)beta) * rho;
     if (!(br < 0.95))
         return fail(GEMHIP_E_NOTCONVERGED, "hope: beta*rho(A) ~ %.3f >= 0.95: the Katz series (I - beta A)^-1 = sum (beta A)^t does not converge fast "
                                            "enough on this graph (the reference forms the dense inverse); lower beta", br);
-    int terms = (br <= 0.0) ? 0 : (int)std::ceil(std::log(1e-8) / std::log(br));
-    terms = std::max(1, std::min(terms, 400));
-    P.terms = terms; P.br = br;
+    P.terms = katz_terms(br); P.br = br;
     return GEMHIP_OK;
 }
 
@@ -1794,15 +1547,8 @@ extern "C" int gemhip_lap_eigmap(int64_t n, int64_t nnz, const int64_t *row_ptr,
     GEMHIP_REQUIRE(k >= 1 && k < n && V_out && eigvals, "lap_eigmap: need 1 <= k < n and output buffers");
     GEMHIP_REQUIRE(oversample >= 0 && krylov_steps >= 1 && max_restarts >= 0, "lap_eigmap: bad solver parameters");
     Hope H; H.beta = 1.0f; H.mode = 1;
-    std::vector<double> dinv(n, 0.0);
-    for (int64_t i = 0; i < n; ++i) {
-        double deg = 0.0;
-        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) deg += w ? w[e] : 1.0;
-        dinv[i] = deg > 0.0 ? 1.0 / std::sqrt(deg) : 0.0;       // networkx: isolated nodes get 0
-    }
     std::vector<float> va(std::max<int64_t>(nnz, 1));
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) va[e] = (float)(dinv[i] * (w ? w[e] : 1.0) * dinv[col[e]]);
+    lap_edge_values(n, row_ptr, col, w, va.data());
     if (upload_csr(H, "lap_eigmap", n, nnz, row_ptr, col, va.data(), nullptr)) return H.err;
     std::vector<float> sig(k);
     if (const int rc = solve_operator(H, true, k, oversample, krylov_steps, max_restarts, tol, seed, 0, 0.0, 1, nullptr, V_out, sig.data(), stats)) return rc;
@@ -1826,11 +1572,7 @@ extern "C" int gemhip_lle(int64_t n, int64_t nnz, const int64_t *row_ptr, const 
     GEMHIP_REQUIRE(oversample >= 0 && krylov_steps >= 1 && max_restarts >= 0, "lle: bad solver parameters");
     Hope H; H.mode = 2;
     std::vector<float> va(std::max<int64_t>(nnz, 1));
-    for (int64_t i = 0; i < n; ++i) {
-        double l1 = 0.0;
-        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) l1 += std::fabs(w ? w[e] : 1.0);
-        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) va[e] = l1 > 0.0 ? (float)((w ? w[e] : 1.0) / l1) : 0.f;   // sklearn normalize(norm='l1')
-    }
+    lle_edge_values(n, row_ptr, w, va.data());
     const CsrT T = transpose_csr(n, nnz, row_ptr, col, va.data());
     if (upload_csr(H, "lle", n, nnz, row_ptr, col, va.data(), &T)) return H.err;
     // c >= sigma_max(I - P)^2 by power iteration on N^T N (at most 60 steps), with a 5 % margin

@@ -40,12 +40,56 @@ def _chol_coef(G):
     return np.linalg.inv(R) * d[:, None]
 
 
+def katz_f(beta, x):
+    return beta * x / (1.0 - beta * x)
+
+
+# The scheduling rules of the eigen-path as functions of their own: tests/test_hope_host.py compares each with its C++ counterpart in
+# gem_amd/csrc/hope_host.hip (sym_cycle_plan, sym_lock_count, sym_next_interval, wanted_values) on the same inputs.
+def cycle_plan(lo, hi, L, th, nl, cyc, amp, amp0, max_degree):
+    """(c, e, q, m): centre and half width of the damped interval, in-filter deflation period, degree."""
+    c, e = 0.5 * (hi + lo), 0.5 * (hi - lo)
+    tmax = max(L - c, c + L) / e
+    rho = tmax + np.sqrt(max(tmax * tmax - 1, 0.0))
+    q = int(max(1, np.floor(np.log(1e6) / np.log(max(rho, 1.0001)))))
+    rho_m = rho
+    if nl and cyc > 0 and len(th):
+        ta = min(tmax, max(1.0, 1.02 * np.abs(np.asarray(th) - c).max() / e))
+        rho_m = ta + np.sqrt(max(ta * ta - 1, 0.0))
+    m = int(max(2, min(max_degree, np.floor(np.log(amp0 if cyc == 0 else amp) / np.log(max(rho_m, 1.0001))))))
+    return c, e, q, m
+
+
+def lock_count(want, b_min, th, res, lock_tol):
+    newl = 0
+    while newl < want - 1 and newl < len(th) - b_min and res[newl] < lock_tol * abs(th[newl]):
+        newl += 1
+    return newl
+
+
+def next_interval(beta, L, want_left, th, tau_prev):
+    """(jc, tau, lo, hi) from the Ritz |f| in the middle of the oversampling columns; tau never falls."""
+    jc = max(0, min(len(th) - 1, want_left + (len(th) - want_left) // 2 - 1))
+    tau = max(tau_prev, abs(katz_f(beta, th[jc])))
+    if not tau > 0:
+        return jc, tau, -L, 0.5 * L
+    hi = min(tau / (abs(beta) * (1 + tau)), 0.98 * L)
+    lo = -min(L, tau / (abs(beta) * (1 - tau)) if tau < 1 else L)
+    return jc, tau, min(lo, -1e-6 * L), hi
+
+
+def wanted_values(beta, qlam, th, k, sig_old):
+    """(sig, change): the k largest |f| over the locked eigenvalues and the active Ritz values, and their largest move relative to sig[0]."""
+    sig = np.sort(np.abs(katz_f(beta, np.concatenate([np.asarray(qlam, np.float64), th]))))[::-1][:k]
+    return sig, (np.abs(sig - sig_old).max() / sig[0] if sig[0] > 0 else 0.0)
+
+
 def sym_filter_svd(A, beta, k, oversample=16, tol=1e-5, max_cycles=60, amp=1e4, amp0=1e3, max_degree=32, seed=0, L=None, trace=None, fused_rr=True):
     """A: scipy CSR float32, symmetric.  Returns (sigma descending [k], U [n,k], V [n,k], info).
     fused_rr (the kernel's default since round 4): the second CholeskyQR pass is not applied to the block; G2 = Y1^T Y1 and H1 = Y1^T A Y1 come from
     one round trip, C2 = chol(G2)^-1 and C2^T H1 C2 are formed in fp64 and the Ritz rotation uses the coefficients C2 W."""
     n = A.shape[0]
-    f = lambda x: beta * x / (1.0 - beta * x)
+    f = lambda x: katz_f(beta, x)
     b = min(k + oversample, n)
     rng = np.random.RandomState(seed)
     if L is None:                                   # hope_setup: power iteration on A^T A, + 10 %
@@ -72,22 +116,14 @@ def sym_filter_svd(A, beta, k, oversample=16, tol=1e-5, max_cycles=60, amp=1e4, 
             Y0, Y1 = Y1, np.float32(2 / e) * spmm(Y1) + np.float32(-2 * c / e) * Y1 - Y0
         return Y1
 
-    V = _orth_scaled(rng.randn(n, b).astype(np.float32), 2)
+    V = _orth_scaled(rng.randn(n, b).astype(np.float32), 1)
     Q = np.zeros((n, 0), np.float32); qlam = []
     lo, hi, tau_prev = -L, 0.5 * L, 0.0
     lock_tol = 0.1 * np.sqrt(max(tol, 1e-12)); b_min = min(b, oversample + 2)
     sig_old = np.zeros(k); th = np.zeros(0); converged = False
     for cyc in range(max_cycles):
         info['cycles'] = cyc + 1
-        c, e = 0.5 * (hi + lo), 0.5 * (hi - lo)
-        tmax = max(L - c, c + L) / e
-        rho = tmax + np.sqrt(max(tmax * tmax - 1, 0.0))
-        q = int(max(1, np.floor(np.log(1e5) / np.log(max(rho, 1.0001)))))
-        rho_m = rho
-        if Q.shape[1] and cyc > 0 and len(th):
-            ta = min(tmax, max(1.0, 1.02 * np.abs(th - c).max() / e))
-            rho_m = ta + np.sqrt(max(ta * ta - 1, 0.0))
-        m = int(max(2, min(max_degree, np.floor(np.log(amp0 if cyc == 0 else amp) / np.log(max(rho_m, 1.0001))))))
+        c, e, q, m = cycle_plan(lo, hi, L, th, Q.shape[1], cyc, amp, amp0, max_degree)
         V = cheb(V, m, c, e, Q, q)
         C2 = None
         if fused_rr:
@@ -120,8 +156,7 @@ def sym_filter_svd(A, beta, k, oversample=16, tol=1e-5, max_cycles=60, amp=1e4, 
         R = B @ C.astype(np.float32) + V @ (-(C * th)).astype(np.float32)
         V = V @ C.astype(np.float32)
         res = np.linalg.norm(R.astype(np.float64), axis=0)
-        sig = np.sort(np.abs(f(np.concatenate([np.asarray(qlam, np.float64), th]))))[::-1][:k]
-        change = np.abs(sig - sig_old).max() / sig[0]; sig_old = sig
+        sig, change = wanted_values(beta, qlam, th, k, sig_old); sig_old = sig
         nl, ma = Q.shape[1], V.shape[1]; want = k - nl
         rmax = (res[:min(want, ma)] / np.maximum(np.abs(th[:min(want, ma)]), 1e-3 * L)).max()
         if trace is not None:
@@ -129,19 +164,10 @@ def sym_filter_svd(A, beta, k, oversample=16, tol=1e-5, max_cycles=60, amp=1e4, 
         if cyc > 0 and change < tol and rmax < 1e-2:
             converged = True
             break
-        newl = 0
-        while newl < want - 1 and newl < ma - b_min and res[newl] < lock_tol * abs(th[newl]):
-            newl += 1
+        newl = lock_count(want, b_min, th, res, lock_tol)
         if newl:
             Q = np.concatenate([Q, V[:, :newl]], axis=1); qlam += list(th[:newl]); V, th = V[:, newl:], th[newl:]
-        want_left = k - Q.shape[1]
-        jc = max(0, min(len(th) - 1, want_left + (len(th) - want_left) // 2 - 1))
-        tau = max(tau_prev, abs(f(th[jc]))); tau_prev = tau
-        if not tau > 0:
-            lo, hi = -L, 0.5 * L
-            continue
-        hi = min(tau / (abs(beta) * (1 + tau)), 0.98 * L)
-        lo = -min(L, tau / (abs(beta) * (1 - tau)) if tau < 1 else L)
+        _, tau_prev, lo, hi = next_interval(beta, L, k - Q.shape[1], th, tau_prev)
     info['converged'] = converged
     lam = np.concatenate([np.asarray(qlam, np.float64), th]); W = np.concatenate([Q, V], axis=1)
     order = np.argsort(-np.abs(f(lam)), kind='stable')[:k]

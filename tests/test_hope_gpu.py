@@ -181,6 +181,30 @@ def test_symmetric_eigen_path_agrees_with_the_block_krylov_path(monkeypatch):
     assert m._stats['solver'] == 'block_krylov'
 
 
+def test_eigen_path_unfused_rayleigh_ritz_agrees_with_the_fused_one(monkeypatch):
+    """GEMHIP_HOPE_SYM_FUSED_RR=0 keeps the two-pass CholeskyQR, the plain Rayleigh-Ritz step and the three-GEMM residuals of the eigen-path
+    (the A/B branch of sym_filter_svd, which no other test reaches): same singular values and community vectors as the fused default, at the
+    bars test_symmetric_eigen_path_agrees_with_the_block_krylov_path sets between solver paths."""
+    g = sbm_graph(2048, 20480, 8, seed=11)
+    k = 16
+    monkeypatch.setenv('GEMHIP_HOPE_SYM', '1')
+    out = {}
+    for fused in (None, '0'):
+        if fused is None:
+            monkeypatch.delenv('GEMHIP_HOPE_SYM_FUSED_RR', raising=False)
+        else:
+            monkeypatch.setenv('GEMHIP_HOPE_SYM_FUSED_RR', fused)
+        m = HOPE(d=2 * k, beta=0.01)
+        Y = m.learn_embedding(graph=g, is_weighted=True, no_python=True)
+        assert m._stats['solver'] == 'symmetric_chebyshev_filter'
+        out[fused] = (Y, m._sigma.copy())
+    assert np.allclose(out[None][1], out['0'][1], rtol=5e-5), np.abs(out[None][1] / out['0'][1] - 1).max()
+    for j in range(k - 1, k - 9, -1):                      # the 8 separated community triplets, vector by vector
+        for half in (0, k):
+            a, b = out[None][0][:, half + j], out['0'][0][:, half + j]
+            assert np.dot(a, b) / (np.linalg.norm(a) * np.linalg.norm(b)) > 1 - 1e-4
+
+
 def test_symmetric_eigen_path_two_sided_spectrum(monkeypatch):
     """A weighted bipartite graph has the spectrum +-lambda: the k largest |f(lambda)| mix both ends (f(x) = beta x / (1 - beta x) favours
     the positive one), and a negative eigenvalue gives u = -v.  Eigen-path (forced) against the block-Krylov path."""
