@@ -3,7 +3,8 @@
 //   sgns_hogwild.hip  sgns_win_kernel<.., DELTA = true, ..>   the shipped Hogwild path (delta write-back, reload-on-update, hot rows)
 //   sgns_det.hip      sgns_win_kernel<.., DELTA = false, ..> + sgns_kernel   deterministic / single-wavefront launches and d >= 384
 //   sgns_part.hip     sgns_win_kernel<.., PART = true>   one bucket (SynPos partition g x SynNeg partition h) of the partitioned N-GPU schedule
-//   n2v.hip           the C ABI (gemhip_sgns_train / gemhip_sgns_train_part pick a launcher), walks, alias tables
+//   sgns_api.hip      the C ABI (gemhip_sgns_train / gemhip_sgns_train_part pick a launcher), unigram tables, hot key, knobs
+//   n2v.hip           no SGNS kernel: walks, alias tables, counts (it shares the Philox and hash helpers below)
 //   sgns_plan.hip     no kernel: the host arithmetic (launch rule, unigram tables; sgns_plan.hpp also defines the constants and row sizes shared with it)
 // Every kernel template is instantiated in exactly one of them; the helpers below are inlined wherever they are used.
 #pragma once
@@ -57,6 +58,18 @@ struct SgnsArgs {
 };
 
 using sgns_fn = void (*)(const SgnsArgs &, int blocks, int threads, size_t lds, hipStream_t);
+// The width rule of every picker below, once (host only): a lane holds VEC floats of a chunk -- 2 when d is even (128-float chunks), 1 when it is odd (64) --
+// and a row is NV = sgns_win_nv(d) chunks, 1, 2 or 4.  Returns pick(VEC, NV) as compile-time constants, or nullptr when d is unsupported (even d <= 512,
+// odd d <= 256).  pick: a generic lambda `[](auto vec, auto nv) -> sgns_fn { return launcher<vec(), nv()>; }`.
+template <class Pick>
+sgns_fn sgns_pick_width(int d, Pick pick)
+{
+    using one = std::integral_constant<int, 1>; using two = std::integral_constant<int, 2>; using four = std::integral_constant<int, 4>;
+    if (d < 1 || d > (d % 2 == 0 ? 512 : 256)) return nullptr;
+    const int nv = sgns_win_nv(d);
+    if (d % 2 == 0) return nv == 1 ? pick(two(), one()) : nv == 2 ? pick(two(), two()) : pick(two(), four());
+    return nv == 1 ? pick(one(), one()) : nv == 2 ? pick(one(), two()) : pick(one(), four());
+}
 sgns_fn pick_sgns(int d);                    // sgns_det.hip: sgns_kernel (no LDS window), nullptr when d is unsupported (even d <= 512, odd d <= 256)
 sgns_fn pick_sgns_win_det(int d);            // sgns_det.hip: sgns_win_kernel, overwrite on leave (bit-compatible with sgns_kernel on one wavefront)
 sgns_fn pick_sgns_win_hogwild(int d);        // sgns_hogwild.hip: sgns_win_kernel, delta write-back

@@ -5,27 +5,11 @@
 namespace gemhip {
 sgns_fn pick_sgns_win_det(int d)
 {
-    if (d % 2 == 0) {
-        const int nv = (d + 127) / 128;
-        return nv <= 1 ? launch_sgns_win<2, 1, false> : nv <= 2 ? launch_sgns_win<2, 2, false> : nv <= 4 ? launch_sgns_win<2, 4, false> : nullptr;
-    }
-    const int nv = (d + 63) / 64;
-    return nv <= 1 ? launch_sgns_win<1, 1, false> : nv <= 2 ? launch_sgns_win<1, 2, false> : nv <= 4 ? launch_sgns_win<1, 4, false> : nullptr;
+    return sgns_pick_width(d, [](auto vec, auto nv) -> sgns_fn { return launch_sgns_win<vec(), nv(), false>; });
 }
 
 sgns_fn pick_sgns(int d)
 {
-    if (d % 2 == 0) {
-        const int nv = (d + 127) / 128;
-        if (nv <= 1) return launch_sgns<2, 1>;
-        if (nv <= 2) return launch_sgns<2, 2>;
-        if (nv <= 4) return launch_sgns<2, 4>;
-        return nullptr;
-    }
-    const int nv = (d + 63) / 64;
-    if (nv <= 1) return launch_sgns<1, 1>;
-    if (nv <= 2) return launch_sgns<1, 2>;
-    if (nv <= 4) return launch_sgns<1, 4>;
-    return nullptr;
+    return sgns_pick_width(d, [](auto vec, auto nv) -> sgns_fn { return launch_sgns<vec(), nv()>; });
 }
 }  // namespace gemhip

@@ -5,11 +5,6 @@
 namespace gemhip {
 sgns_fn pick_sgns_win_hogwild(int d)
 {
-    if (d % 2 == 0) {
-        const int nv = (d + 127) / 128;
-        return nv <= 1 ? launch_sgns_win<2, 1, true> : nv <= 2 ? launch_sgns_win<2, 2, true> : nv <= 4 ? launch_sgns_win<2, 4, true> : nullptr;
-    }
-    const int nv = (d + 63) / 64;
-    return nv <= 1 ? launch_sgns_win<1, 1, true> : nv <= 2 ? launch_sgns_win<1, 2, true> : nv <= 4 ? launch_sgns_win<1, 4, true> : nullptr;
+    return sgns_pick_width(d, [](auto vec, auto nv) -> sgns_fn { return launch_sgns_win<vec(), nv(), true>; });
 }
 }  // namespace gemhip

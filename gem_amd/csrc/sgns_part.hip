@@ -6,13 +6,7 @@
 namespace gemhip {
 sgns_fn pick_sgns_win_part(int d, bool hogwild)
 {
-    if (d % 2 == 0) {
-        const int nv = (d + 127) / 128;
-        if (hogwild) return nv <= 1 ? launch_sgns_win_part<2, 1, true> : nv <= 2 ? launch_sgns_win_part<2, 2, true> : nv <= 4 ? launch_sgns_win_part<2, 4, true> : nullptr;
-        return nv <= 1 ? launch_sgns_win_part<2, 1, false> : nv <= 2 ? launch_sgns_win_part<2, 2, false> : nv <= 4 ? launch_sgns_win_part<2, 4, false> : nullptr;
-    }
-    const int nv = (d + 63) / 64;
-    if (hogwild) return nv <= 1 ? launch_sgns_win_part<1, 1, true> : nv <= 2 ? launch_sgns_win_part<1, 2, true> : nv <= 4 ? launch_sgns_win_part<1, 4, true> : nullptr;
-    return nv <= 1 ? launch_sgns_win_part<1, 1, false> : nv <= 2 ? launch_sgns_win_part<1, 2, false> : nv <= 4 ? launch_sgns_win_part<1, 4, false> : nullptr;
+    if (hogwild) return sgns_pick_width(d, [](auto vec, auto nv) -> sgns_fn { return launch_sgns_win_part<vec(), nv(), true>; });
+    return sgns_pick_width(d, [](auto vec, auto nv) -> sgns_fn { return launch_sgns_win_part<vec(), nv(), false>; });
 }
 }  // namespace gemhip

@@ -2,11 +2,27 @@
 // a bucket launch of the partitioned schedule, and the unigram alias tables of InitUnigramTable in both layouts, for one table or one per partition.
 // HIP-free by rule: no HIP header, nothing from common.hpp -- the `.hip` suffix only serves the build's csrc/*.hip glob, and the file is also valid
 // `clang++ -x c++ -std=c++17` input (scripts/build_asan_plan.sh runs it under AddressSanitizer / UBSan with a driver of its own, tests/test_sgns_plan.py
-// compares that driver's output with tests/golden/sgns_plan_grid.txt and the tables with the oracle's).  n2v.hip holds the C ABI around it.
+// compares that driver's output with tests/golden/sgns_plan_grid.txt and the tables with the oracle's).  sgns_api.hip holds the C ABI around it.
 #include "sgns_plan.hpp"
 #include "../../include/gem_hip.h"
+#include <cstdlib>
 
 namespace gemhip {
+
+SgnsKnobs sgns_knobs_from_env(const char *(*lookup)(const char *))
+{
+    SgnsKnobs kn;
+    if (const char *e = lookup("GEMHIP_SGNS_MAX_WAVES")) kn.max_waves = std::max(0, atoi(e));
+    if (const char *e = lookup("GEMHIP_SGNS_CACHE_R")) kn.cache_radius = std::min(31, std::max(-1, atoi(e)));
+    if (const char *e = lookup("GEMHIP_SGNS_CACHE_DELTA")) kn.cache_delta = std::min(1, std::max(-1, atoi(e)));
+    if (const char *e = lookup("GEMHIP_SGNS_PREFETCH")) kn.prefetch = std::min(2, std::max(1, atoi(e)));
+    if (const char *e = lookup("GEMHIP_SGNS_RELOAD")) kn.reload = atoi(e) != 0;
+    if (const char *e = lookup("GEMHIP_SGNS_HOT_COUNT")) kn.hot_count = std::max(-1, atoi(e));
+    if (const char *e = lookup("GEMHIP_SGNS_LOCAL_HOT")) kn.local_hot = std::max(0, atoi(e));
+    if (const char *e = lookup("GEMHIP_SGNS_FRESH")) kn.fresh = atoi(e) & 7;
+    if (const char *e = lookup("GEMHIP_SGNS_NEG_COUNT")) kn.neg_count = std::max(0, atoi(e));
+    return kn;
+}
 
 // Which kernel, how many concurrent wavefronts and which rows are "hot" for one pass of TrainModel over `nwalks` walks.  Pure host arithmetic.
 //
@@ -85,7 +101,7 @@ SgnsLaunchPlan plan_sgns_launch(const VocabStats &vs, const SgnsKnobs &kn, int64
         // sum_v (p_v + 5 q_v)^2 (p = token share: the context; q = unigram^0.75 share: the five negatives) -- minus the 40 / active a table of equally frequent
         // rows has, so that SBM graphs stay on the rho rule they were validated on.  What round 6 found out about it (profiles/r06_*.jsonl):
         //  * the bound was fitted through launches whose gaps were dominated by a HEAVY TAIL that has nothing to do with hubs: an isolated edge trained by two
-        //    wavefronts at once (LOCALLY HOT ROWS, n2v.hip build_hotkey -- now handled; launches at one width agree to 0.2 % where they scattered over 6 %);
+        //    wavefronts at once (LOCALLY HOT ROWS, sgns_api.hip build_hotkey -- now handled; launches at one width agree to 0.2 % where they scattered over 6 %);
         //  * the staleness of the hubs' gradients is not the cause either: instrumented (GEMHIP_SGNS_STALENESS), the top hub's row takes 22 foreign updates
         //    between a wavefront's read and its add at 768 wavefronts; fresh reads / returning atomics cut that to 6 and the gap does not move; making every
         //    Hogwild write a lossless add makes it slightly WORSE; lowering the hot-row threshold 2-16x makes it worse and slower;

@@ -1,5 +1,5 @@
 // sgns_plan.hpp -- the host arithmetic of SGNS (sgns_plan.hip): the Hogwild launch rule and the unigram alias tables.  Plain C++, no HIP:
-// everything here runs on a CPU (scripts/build_asan_plan.sh, tests/test_sgns_plan.py), n2v.hip only uploads and launches what it returns.
+// everything here runs on a CPU (scripts/build_asan_plan.sh, tests/test_sgns_plan.py), sgns_api.hip only uploads and launches what it returns.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -90,12 +90,15 @@ struct SgnsKnobs {
     bool part = false;                // a bucket launch of the partitioned schedule (sgns_win_kernel<PART>: as-loaded window copies in global scratch, 3 wavefronts per SIMD)
     double duty = 1.0;                // fraction of a wavefront's time spent in pair steps (negative rows open); < 1 only for the buckets of the partitioned schedule
     double touch_scale = 1.0;         // factor on VocabStats::touch2 (bucket launches: the pairs of ONE bucket touch the rows of two partitions only: parts x duty)
-    bool has_local_hot = false;       // this corpus HAS locally hot nodes (n2v.hip build_hotkey): the launch carries the staging row and a hot threshold even without count-hot rows
+    bool has_local_hot = false;       // this corpus HAS locally hot nodes (sgns_api.hip build_hotkey): the launch carries the staging row and a hot threshold even without count-hot rows
     int32_t local_hot = 8;            // LOCALLY HOT ROWS: a node with at least this many tokens per walk that contains it is treated as a hot row (0: off)
     int32_t neg_count = 0;            // fresh bit 2: token count from which a negative row is updated by atomic add (0: every row)
     int32_t fresh = 0;                // FRESH HOT ROWS (sgns.hpp, SgnsArgs::fresh): bit 0 hot centre words by returning atomics, bit 1 hot negatives re-read before the dot products
     bool node_id_layout = false;      // the unigram table the launch draws from is in node-id order (gemhip_n2v_build_unigram), not the binary's: half the concurrent-touch bound (plan_sgns_launch)
 };
+// The A/B overrides of a new handle's knobs: the GEMHIP_SGNS_* variables as `lookup` answers for them (gemhip_n2v_create passes getenv, once; the
+// launch path reads no environment), each clamped to its knob's range; a variable `lookup` does not know leaves the default.
+SgnsKnobs sgns_knobs_from_env(const char *(*lookup)(const char *));
 // ... and what a launch of TrainModel over `nwalks` walks then looks like
 struct SgnsLaunchPlan {
     bool window = false;              // sgns_win_kernel (LDS window) or sgns_kernel

@@ -213,3 +213,62 @@ def test_locally_hot_rows_reach_the_bucket_launches():
     Pb = multi_gpu.Node2VecPartitioned(b, multi_gpu.TorchComm(1), 0, 1, n, 2, 40, 5, 1, seed=3, flags=9 | 4, episodes=2).run_virtual(2).cpu().numpy()
     assert np.array_equal(Pa, Pb)
     b.close()
+
+
+@pytest.mark.parametrize('d', [16, 130])
+def test_one_handle_serves_both_table_sets_and_both_layouts(d):
+    """A handle holds two sets of unigram tables -- the single one of gemhip_sgns_train and the per-partition one of gemhip_sgns_train_part -- and
+    either in two layouts, each with a slot table built on first use.  Deterministic launches on one wavefront, 2 walks of 13 tokens per node, window 3:
+    (a) building the two-partition tables and training a bucket leaves the single table's launches as they were: the same start tables give the
+        same result, bit for bit, without a rebuild;
+    (b) after a launch in the binary's layout, a build in the node-id layout trains exactly what a fresh handle trains: the second launch does not
+        draw from the first layout's slot table."""
+    from test_oracle_n2v import small_graph
+    n, src, dst, _ = small_graph(False, seed=3, n=200, m=3000)
+    row_ptr, col, _ = oracle.sorted_csr(n, src, dst, None)
+    L, l, window, seed = _hip.lib(), 13, 3, 3
+    rs = np.random.RandomState(d)
+    P0, N0 = (0.05 * rs.randn(n, d)).astype(np.float32), (0.05 * rs.randn(n, d)).astype(np.float32)
+
+    def handle():
+        h, m = C.c_void_p(), C.c_int64()
+        _hip.check(L.gemhip_n2v_create(n, len(col), _hip.ptr(row_ptr, C.c_int64), _hip.ptr(col, C.c_int32), None, C.byref(h)))
+        _hip.check(L.gemhip_n2v_start_nodes(h, C.byref(m)))
+        _hip.check(L.gemhip_n2v_walks(h, 1.0, 1.0, 2, l, seed, 11, 0, 2 * m.value, None))
+        _hip.check(L.gemhip_n2v_vocab(h, None))
+        _hip.check(L.gemhip_sgns_init(h, d, seed, None, None))
+        return h, 2 * m.value
+
+    def train(h, nwalks, flags):
+        """one epoch of gemhip_sgns_train from the fixed start tables -> (SynPos, SynNeg)"""
+        _hip.check(L.gemhip_sgns_set_tables(h, _hip.ptr(P0, C.c_float), _hip.ptr(N0, C.c_float)))
+        _hip.check(L.gemhip_sgns_train(h, window, 5, 0.025, 1, 0, 0, nwalks, nwalks * l, 0, seed, flags | 4, None))
+        P, N = np.empty_like(P0), np.empty_like(N0)
+        _hip.check(L.gemhip_sgns_get_tables(h, _hip.ptr(P, C.c_float), _hip.ptr(N, C.c_float)))
+        return P, N
+
+    h, nwalks = handle()
+    _hip.check(L.gemhip_n2v_build_unigram(h, None, None, None))
+    T = train(h, nwalks, 11)
+    assert not np.array_equal(T[0], P0) and not np.array_equal(T[1], N0)
+    # (a) the same handle: two-partition tables, one bucket, then the single table again
+    _hip.check(L.gemhip_n2v_build_unigram_parts(h, 2, None, None))
+    Pp = torch.from_numpy(P0[0::2].copy()).cuda(); Np = torch.from_numpy(N0[1::2].copy()).cuda()
+    walks, nw, wl = C.c_void_p(), C.c_int64(), C.c_int32()
+    _hip.check(L.gemhip_n2v_walks_ptr(h, C.byref(walks), C.byref(nw), C.byref(wl)))
+    _hip.check(L.gemhip_sgns_train_part(h, walks, nwalks, l, None, 0, 0, 0, window, 0.025, nwalks * l, 0, 0, seed, 11 | 4, 0, 1, C.c_void_p(Pp.data_ptr()),
+                                          C.c_void_p(Np.data_ptr()), d, None))
+    torch.cuda.synchronize()
+    assert not np.array_equal(Pp.cpu().numpy(), P0[0::2])                 # (the bucket did train)
+    again = train(h, nwalks, 11)
+    assert np.array_equal(again[0], T[0]) and np.array_equal(again[1], T[1])
+    _hip.check(L.gemhip_n2v_destroy(h))
+    # (b) one handle: the binary's layout, a launch, then the node-id layout
+    h, nwalks = handle()
+    _hip.check(L.gemhip_n2v_build_unigram_vocab_order(h, 11, None, None, None, None))
+    V = train(h, nwalks, 27)
+    assert not np.array_equal(V[1], T[1])                                 # (the layouts are different tables: different negatives)
+    _hip.check(L.gemhip_n2v_build_unigram(h, None, None, None))
+    again = train(h, nwalks, 11)
+    assert np.array_equal(again[0], T[0]) and np.array_equal(again[1], T[1])
+    _hip.check(L.gemhip_n2v_destroy(h))
