@@ -50,6 +50,8 @@ _SIGS = {
     'gemhip_gf_plan_sweeps': (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
     'gemhip_gf_plan_set_rows_per_wave': (C.c_int, [C.c_void_p, C.c_int32]),
     'gemhip_gf_plan_set_fused_sweeps': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    'gemhip_gf_plan_set_hub_block': (C.c_int, [C.c_void_p, C.c_int32]),
+    'gemhip_gf_plan_hub_block': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), i64p]),
     'gemhip_gf_plan_get_embedding': (C.c_int, [C.c_void_p, f32p]),
     'gemhip_gf_plan_current': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     'gemhip_gf_plan_info': (C.c_int, [C.c_void_p, i64p]),

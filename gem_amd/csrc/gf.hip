@@ -65,6 +65,9 @@ struct gemhip_gf_plan {
     // Auto: 2 on the K-rows-per-wavefront kernel (the big levels), 0 on the one-row kernel (small, L2-resident levels, where nothing needs evicting).
     // A hint only: results are bit-identical either way.
     int nt_store = getenv("GEMHIP_GF_NT_STORE") ? atoi(getenv("GEMHIP_GF_NT_STORE")) : -1;
+    // 1: hub rows run gf_hub_block_kernel (blocks of B edges through a Gram matrix) instead of gf_hub_kernel -- opt-in, within the oracle tolerance but not
+    // bit-identical to the row kernels (GEMHIP_GF_HUB_BLOCK=1 read per plan, gemhip_gf_plan_set_hub_block)
+    int hub_block = getenv("GEMHIP_GF_HUB_BLOCK") && atoi(getenv("GEMHIP_GF_HUB_BLOCK")) == 1 ? 1 : 0;
     // Unit schedule (gemhip_gf_plan_create_any_order on a list the row schedule cannot represent): the same arrays, read differently (GfHostPlan);
     // nrows counts units.
     bool units = false;
@@ -478,6 +481,232 @@ void launch_hub(const gemhip_gf_plan *p, int64_t row0, int64_t nhub, const float
                            (int)p->d, eta, regu);
 }
 
+// ---- blocked hub rows (gemhip_gf_plan_set_hub_block; opt-in, NOT bit-identical to the row kernels).  gf_hub_kernel takes the memory latency out of a
+// hub row's chain; what remains is the chain: per edge one dot product, a wave reduction, a scalar and an axpy, each waiting for the one before.
+// Within one row's pass every neighbour row is constant (only row i is written), so the update is affine in x_i, and B edges (neighbour rows y_t,
+// weights w_t, a = 1 - eta * regu) can be applied at once: with G = Y Y^T and p = Y x_0,
+//     s_t = w_t - a^(t-1) p_t - eta * sum_{u<t} a^(t-1-u) s_u G_tu,        x_B = a^B x_0 + sum_u (eta * a^(B-u) s_u) y_u.
+// The producers stage B neighbour rows in LDS as gf_hub_kernel's do and form G on the matrix units with the fp32-input MFMA (exact fp32); G does
+// not depend on x, so it runs ahead of the chain.  The consumer wavefront computes p (lane = row of the block, 64 / B lanes share a row and each
+// reads a contiguous piece of it), runs the B-step substitution without any reduction -- lane v keeps r_v = x_t . y_v up to date with
+// r_v <- r_v - (eta regu) r_v + eta s_t G_vt, one broadcast and two FMAs per step -- and applies the GEMV.  The powers of a that scale x and the
+// coefficients come from gf_hub_decay (evaluated in double, hi + lo where they scale x).  No atomics, one fixed summation order: a row's result
+// depends only on its edge list and its inputs, not on the producer count or on timing.
+struct GfHubDecay { float hi[GF_HUB_BLOCK_MAX + 1], lo[GF_HUB_BLOCK_MAX + 1]; };
+typedef float gf_f32x2 __attribute__((ext_vector_type(2)));
+typedef float gf_f32x4 __attribute__((ext_vector_type(4)));
+typedef float gf_f32x16 __attribute__((ext_vector_type(16)));
+
+template <int VEC, int NV, int NP> struct gf_hub_block_cfg {
+    static constexpr int RW = NV * VEC * WAVE;                 // floats of one staged row
+    static constexpr int B = gf_hub_block_of_row_floats(RW);   // edges per block
+    // rows are 4 floats apart from a multiple of 64: the 16 lanes of a ds_read_b128 group that read 16 different rows at one column hit 16
+    // different 16-byte slots of the 256-byte bank row (the access pattern of p = Y x and of the MFMA operand reads)
+    static constexpr int RS = RW + 4;
+    static constexpr int NSEG = WAVE / B;                      // lanes per row of the block ...
+    static constexpr int L = RW / NSEG;                        // ... each reading this many contiguous floats of it
+    static constexpr int STAGE = B * RS + B * B + B;           // floats of one ring stage: the rows, G, the weights
+    // stages: what fits 64 KB with the rest of the workgroup's LDS, so that two hub rows share a CU (160 KB) as gf_hub_kernel's do -- on a power-law
+    // graph the hub rows together, not only the longest, set the sweep time (1024 rows of 4096 edges: 1.01 ms at one workgroup per CU against 0.66 ms
+    // of gf_hub_kernel at two); at least 2, which for the widest rows is one workgroup per CU
+    static constexpr int FIT = (64 * 1024 - NSEG * (L + 4) * 4 - 64) / (STAGE * 4);
+    static constexpr int NST = FIT > NP ? NP : FIT < 2 ? 2 : FIT;
+    static constexpr int PF0 = 64 / (NV * VEC);                // neighbour rows a producer has in flight: 64 registers' worth, 2 .. B
+    static constexpr int PF = PF0 > B ? B : PF0 < 2 ? 2 : PF0;
+    static_assert(B <= GF_HUB_BLOCK_MAX && B % PF == 0 && L % 4 == 0 && (NST * STAGE + NSEG * (L + 4)) * 4 + 64 <= 160 * 1024, "LDS layout");
+};
+
+template <int VEC, int NV, int NP>
+__global__ __launch_bounds__((NP + 1) * 64) void gf_hub_block_kernel(const int32_t *__restrict__ rows, const int64_t *__restrict__ ptr,
+                                                                     const uint32_t *__restrict__ col, const float *__restrict__ w, const float *Xold,
+                                                                     float *Xnew, int64_t row0, int d, float eta, float regu, GfHubDecay dec)
+{
+    using cfg = gf_hub_block_cfg<VEC, NV, NP>;
+    constexpr int B = cfg::B, RS = cfg::RS, L = cfg::L, STAGE = cfg::STAGE, NST = cfg::NST, PF = cfg::PF;
+    __shared__ __attribute__((aligned(16))) float ring[NST * STAGE];
+    __shared__ __attribute__((aligned(16))) float xs[cfg::NSEG * (L + 4)];        // x_0 of the block, each lane group's piece 4 floats further (banks)
+    __shared__ int32_t ready[NST];
+    __shared__ int32_t done;
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    const int row = lane % B, seg = lane / B;
+    const int64_t r = row0 + blockIdx.x;
+    const int32_t i = rows[r];
+    const int64_t e0 = ptr[r], e1 = ptr[r + 1];
+    const int nb = __builtin_amdgcn_readfirstlane((int)((e1 - e0 + B - 1) / B));
+    if (threadIdx.x == 0) done = 0;
+    if (threadIdx.x < NST) ready[threadIdx.x] = 0;
+    __syncthreads();
+    if (wave == 0) {
+        float xi[NV][VEC];
+        const float *pi = Xold + (int64_t)i * d;
+#pragma unroll
+        for (int c = 0; c < NV; ++c) load_row<VEC>(pi, d, lane, c, xi[c]);
+        const float el = __fmul_rn(eta, regu);
+        const float tab_hi = dec.hi[lane < B ? lane : B], tab_lo = dec.lo[lane < B ? lane : B];       // lane k holds a^k
+        const float hi_full = dec.hi[B], lo_full = dec.lo[B], hrev_full = dec.hi[B - 1 - row];
+        for (int t = 0; t < nb; ++t) {
+            const int sb = t % NST;
+            const int64_t left = e1 - (e0 + (int64_t)t * B);
+            const int m = __builtin_amdgcn_readfirstlane((int)(left < B ? left : B));
+#pragma unroll
+            for (int q = 0; q < NV; ++q)
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const int e = (q * WAVE + lane) * VEC + k;
+                    xs[e + (e / L) * 4] = xi[q][k];
+                }
+            while (gf_flag_ld(&ready[sb]) != t + 1) __builtin_amdgcn_s_sleep(0);
+            asm volatile("" ::: "memory");
+            const float *st = ring + (size_t)sb * STAGE, *Gs = st + B * RS, *ws = Gs + B * B;
+            // p = Y x_0: this lane's piece of row `row`, then the pieces of a row added across its lanes (every lane of a row ends with the same sum)
+            const gf_f32x4 *yr = reinterpret_cast<const gf_f32x4 *>(st + row * RS + seg * L);
+            const gf_f32x4 *xr = reinterpret_cast<const gf_f32x4 *>(xs + seg * (L + 4));
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 8
+            for (int j = 0; j < L / 4; ++j) {
+                const gf_f32x4 y = yr[j], x = xr[j];
+                a0 = fmaf(y.x, x.x, a0); a1 = fmaf(y.y, x.y, a1); a2 = fmaf(y.z, x.z, a2); a3 = fmaf(y.w, x.w, a3);
+            }
+            float rv = __fadd_rn(__fadd_rn(a0, a1), __fadd_rn(a2, a3));
+#pragma unroll
+            for (int o = B; o < WAVE; o <<= 1) rv = __fadd_rn(rv, __shfl_xor(rv, o));
+            // the substitution: rv = x_u . y_row while step u runs.  A last partial block runs all B steps too -- its rows past m repeat row m - 1
+            // with weight 0, finite work whose coefficients are dropped below
+            float g[B];
+#pragma unroll
+            for (int u = 0; u < B; ++u) g[u] = Gs[u * B + row];                    // G is symmetric: column `row` read as a row, lane-contiguous
+            const float ew = __fmul_rn(eta, ws[row]);
+            float esm = 0.f;
+#pragma unroll
+            for (int u = 0; u < B; ++u) {
+                // eta s_u = eta (w_u - x_u . y_u): per step the chain is one broadcast and two FMAs, the decay of rv runs beside it
+                const float es = fmaf(-eta, bcast_lane(rv, u), bcast_lane(ew, u));
+                esm = row == u ? es : esm;
+                rv = fmaf(es, g[u], fmaf(-el, rv, rv));
+            }
+            const int back = m - 1 - row;
+            const float hrev = m == B ? hrev_full : __shfl(tab_hi, back > 0 ? back : 0);
+            const float cm = row < m ? __fmul_rn(esm, hrev) : 0.f;                 // eta a^(m-1-u) s_u
+            const float him = m == B ? hi_full : bcast_lane(tab_hi, m), lom = m == B ? lo_full : bcast_lane(tab_lo, m);
+            // x_m = a^m x_0 + sum_u c_u y_u, the small terms summed first
+            float acc[NV][VEC];
+#pragma unroll
+            for (int q = 0; q < NV; ++q)
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) acc[q][k] = __fmul_rn(lom, xi[q][k]);
+#pragma unroll
+            for (int u = 0; u < B; ++u) {
+                const float cu = bcast_lane(cm, u);
+                const float *yu = st + u * RS;
+#pragma unroll
+                for (int q = 0; q < NV; ++q) {
+                    if constexpr (VEC == 2) {
+                        const gf_f32x2 y = *reinterpret_cast<const gf_f32x2 *>(yu + (q * WAVE + lane) * 2);
+                        acc[q][0] = fmaf(cu, y.x, acc[q][0]); acc[q][1] = fmaf(cu, y.y, acc[q][1]);
+                    } else {
+                        acc[q][0] = fmaf(cu, yu[q * WAVE + lane], acc[q][0]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < NV; ++q)
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) xi[q][k] = fmaf(him, xi[q][k], acc[q][k]);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (lane == 0) gf_flag_st(&done, t + 1);
+        }
+        store_row<VEC, NV>(Xnew + (int64_t)i * d, d, lane, xi, 0);
+    } else {
+        // A workgroup's wavefronts go to the four SIMDs in turn, so wavefront 4 sits on the chain's SIMD: it stays idle.  (As a producer its MFMAs and
+        // LDS reads cost the chain 52 ns per edge against 44.5 ns without it, one 100k-edge row at d = 128; R-MAT-22: 6.19 against 5.88 ms per sweep.)
+        constexpr int NPE = NP > 3 ? NP - 1 : NP;
+        if (NP > 3 && wave == 4) return;
+        const int pid = wave < 4 ? wave - 1 : wave - 2;
+        for (int t = pid; t < nb; t += NPE) {
+            const int sb = t % NST;
+            const int64_t eb = e0 + (int64_t)t * B;
+            const int cnt = __builtin_amdgcn_readfirstlane((int)((e1 - eb) < B ? (e1 - eb) : B));
+            const uint32_t cj = lane < cnt ? col[eb + lane] : 0u;
+            const float wj = lane < cnt ? w[eb + lane] : 0.f;
+            float xj[PF][NV][VEC];
+            auto fetch = [&](int g0) {                                             // rows g0 .. g0 + PF - 1 of the block; past the end: the last edge's row again
+#pragma unroll
+                for (int u = 0; u < PF; ++u) {
+                    const int kk = (g0 + u) < cnt ? (g0 + u) : cnt - 1;
+                    const uint32_t c = bcast_lane(cj, kk);
+                    const float *pj = ((c >> 31) ? Xnew : Xold) + (int64_t)(c & 0x7fffffffu) * d;
+#pragma unroll
+                    for (int q = 0; q < NV; ++q) load_row<VEC>(pj, d, lane, q, xj[u][q]);
+                }
+            };
+            fetch(0);                                                              // travels while the ring stage is still in use
+            while (gf_flag_ld(&done) < t - NST + 1) __builtin_amdgcn_s_sleep(1);   // the block that used this ring stage is consumed
+            asm volatile("" ::: "memory");
+            float *st = ring + (size_t)sb * STAGE, *Gs = st + B * RS;
+#pragma unroll
+            for (int g0 = 0; g0 < B; g0 += PF) {
+#pragma unroll
+                for (int u = 0; u < PF; ++u)
+#pragma unroll
+                    for (int q = 0; q < NV; ++q)
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) st[(g0 + u) * RS + (q * WAVE + lane) * VEC + k] = xj[u][q][k];
+                if (g0 + PF < B) fetch(g0 + PF);
+            }
+            if (lane < B) Gs[B * B + lane] = wj;
+            // G = Y Y^T on the matrix units.  A lane supplies one element of row `row` per instruction, as the A operand and (G's column = a row of Y) as the
+            // B operand alike; WHICH k a lane group supplies is free as long as both operands agree, so each group walks its own contiguous piece
+            const gf_f32x4 *yr = reinterpret_cast<const gf_f32x4 *>(st + row * RS + seg * L);
+            if constexpr (B == 32) {
+                gf_f32x16 acc;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+#pragma unroll 4
+                for (int j = 0; j < L / 4; ++j) {
+                    const gf_f32x4 y = yr[j];
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(y.x, y.x, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(y.y, y.y, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(y.z, y.z, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(y.w, y.w, acc, 0, 0, 0);
+                }
+#pragma unroll
+                for (int q = 0; q < 16; ++q) Gs[((q & 3) + 8 * (q >> 2) + 4 * seg) * B + row] = acc[q];      // C/D map of the 32x32 MFMA
+            } else {
+                gf_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};     // two accumulators: the 16x16x4 form issues faster than it completes
+#pragma unroll 4
+                for (int j = 0; j < L / 4; ++j) {
+                    const gf_f32x4 y = yr[j];
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(y.x, y.x, acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(y.y, y.y, acc1, 0, 0, 0);
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(y.z, y.z, acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(y.w, y.w, acc1, 0, 0, 0);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) Gs[(4 * seg + q) * B + row] = __fadd_rn(acc0[q], acc1[q]);       // C/D map of the 16x16 MFMA
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (lane == 0) gf_flag_st(&ready[sb], t + 1);
+        }
+    }
+}
+
+template <int VEC, int NV>
+void launch_hub_block(const gemhip_gf_plan *p, int64_t row0, int64_t nhub, const float *Xold, float *Xnew, float eta, float regu, const GfHubDecay &dec,
+                      hipStream_t s)
+{
+    // wavefronts per hub row: launch_hub's switch (8 or 4 with the chain's), read per launch here (tests change it in one process); the result does
+    // not depend on it
+    const char *env = getenv("GEMHIP_GF_HUB_PRODUCERS");
+    const int np = env ? atoi(env) : 7;
+    if (np >= 7)
+        hipLaunchKernelGGL((gf_hub_block_kernel<VEC, NV, 7>), dim3((unsigned)nhub), dim3(512), 0, s, p->d_rows, p->d_ptr, p->d_col, p->d_w, Xold, Xnew,
+                           row0, (int)p->d, eta, regu, dec);
+    else
+        hipLaunchKernelGGL((gf_hub_block_kernel<VEC, NV, 3>), dim3((unsigned)nhub), dim3(256), 0, s, p->d_rows, p->d_ptr, p->d_col, p->d_w, Xold, Xnew,
+                           row0, (int)p->d, eta, regu, dec);
+}
+
 // ---- unit schedule (any edge order; gemhip_gf_plan_create_any_order).  A UNIT is a run of one row's edges that one wavefront applies in file order:
 // it loads the row once -- from X_new when the row was already written in this sweep (bit 31 of its entry), else from X_old --, gathers every
 // neighbour from the table bit 31 of d_col names, and stores the row to X_new.  Units of one level touch no common row that one of them writes.
@@ -551,13 +780,16 @@ void launch_units_fused(const gemhip_gf_plan *p, int l0, int l1, const float *Xo
 struct gf_launchers {
     void (*sweep)(const gemhip_gf_plan *, int, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
     void (*hub)(const gemhip_gf_plan *, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
+    void (*hub_block)(const gemhip_gf_plan *, int64_t, int64_t, const float *, float *, float, float, const GfHubDecay &, hipStream_t);
+    int hub_block_edges;      // B of gf_hub_block_kernel at this width
     int (*coop)(const gemhip_gf_plan *, float *, float *, float, float, int, hipStream_t);
     void (*units)(const gemhip_gf_plan *, int64_t, int64_t, const float *, float *, float, float, hipStream_t);
     void (*units_fused)(const gemhip_gf_plan *, int, int, const float *, float *, float, float, hipStream_t);
 };
 template <int VEC, int NV> const gf_launchers *gf_launchers_of()
 {
-    static const gf_launchers L = {launch_sweep<VEC, NV>, launch_hub<VEC, NV>, launch_coop<VEC, NV>, launch_units<VEC, NV>, launch_units_fused<VEC, NV>};
+    static const gf_launchers L = {launch_sweep<VEC, NV>, launch_hub<VEC, NV>, launch_hub_block<VEC, NV>, gf_hub_block_cfg<VEC, NV, 7>::B,
+                                   launch_coop<VEC, NV>, launch_units<VEC, NV>, launch_units_fused<VEC, NV>};
     return &L;
 }
 template <int VEC> const gf_launchers *gf_launchers_of_chunks(int nv)
@@ -797,6 +1029,11 @@ extern "C" int gemhip_gf_plan_sweeps(gemhip_gf_plan_t p, int32_t nsweeps, float 
         return GEMHIP_OK;
     }
     const int nlevels = (int)p->level_off.size() - 1;
+    GfHubDecay decay;                                  // the powers of 1 - eta * regu the blocked hub kernel scales with: eta and regu arrive here
+    if (p->hub_block) {
+        GEMHIP_REQUIRE(p->fn->hub_block_edges == gf_hub_block((int)p->d), "gf_plan_sweeps: block size of d=%lld", (long long)p->d);
+        gf_hub_decay(eta, regu, p->fn->hub_block_edges, decay.hi, decay.lo);
+    }
     int it0 = 0;
     if (p->fused_sweeps > 1 && nlevels == 1 && (p->level_hubs.empty() || p->level_hubs[0] == 0)) {
         // up to fused_sweeps sweeps per cooperative launch; the table of sweep k is X[cur ^ (k & 1)]
@@ -821,7 +1058,8 @@ extern "C" int gemhip_gf_plan_sweeps(gemhip_gf_plan_t p, int32_t nsweeps, float 
                 }
                 GEMHIP_CHECK(hipEventRecord(p->hub_fork, s));
                 GEMHIP_CHECK(hipStreamWaitEvent(p->hub_stream, p->hub_fork, 0));
-                p->fn->hub(p, r0, nh, Xold, Xnew, eta, regu, p->hub_stream);
+                if (p->hub_block) p->fn->hub_block(p, r0, nh, Xold, Xnew, eta, regu, decay, p->hub_stream);
+                else p->fn->hub(p, r0, nh, Xold, Xnew, eta, regu, p->hub_stream);
                 GEMHIP_CHECK(hipEventRecord(p->hub_join, p->hub_stream));
             }
             if (nr - nh > 0) p->fn->sweep(p, l, r0 + nh, nr - nh, Xold, Xnew, eta, regu, s);
@@ -844,6 +1082,22 @@ extern "C" int gemhip_gf_plan_set_fused_sweeps(gemhip_gf_plan_t p, int32_t sweep
 {
     GEMHIP_REQUIRE(p && sweeps_per_launch >= 0 && sweeps_per_launch <= 65536 && max_grid >= 0, "gf_plan_set_fused_sweeps: bad arguments");
     p->fused_sweeps = sweeps_per_launch; p->fused_grid = max_grid;
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_gf_plan_set_hub_block(gemhip_gf_plan_t p, int32_t on)
+{
+    GEMHIP_REQUIRE(p && (on == 0 || on == 1), "gf_plan_set_hub_block: 0 (off) or 1 (on)");
+    if (!p->units) p->hub_block = on;
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_gf_plan_hub_block(gemhip_gf_plan_t p, int32_t *block, int64_t *hub_rows)
+{
+    GEMHIP_REQUIRE(p && block && hub_rows, "gf_plan_hub_block: NULL argument");
+    *block = (p->units || !p->hub_block) ? 0 : p->fn->hub_block_edges;
+    *hub_rows = 0;
+    for (int64_t h : p->level_hubs) *hub_rows += h;
     return GEMHIP_OK;
 }
 

@@ -219,4 +219,29 @@ int gf_level_rows_per_wave(int forced, int64_t maxlen, int64_t nrows, int kmax)
     return (int)std::max<int64_t>(1, std::min<int64_t>(nrows / (2 * 256 * 32), kmax));
 }
 
+int gf_row_floats(int d)
+{
+    if (d < 1) return 0;
+    const int vec = d % 2 == 0 ? 2 : 1, chunks = (d + vec * 64 - 1) / (vec * 64);
+    const int nv = chunks <= 1 ? 1 : chunks <= 2 ? 2 : chunks <= 4 ? 4 : chunks <= 8 ? 8 : 0;
+    return nv * vec * 64;
+}
+
+int gf_hub_block(int d)
+{
+    const int rw = gf_row_floats(d);
+    return rw ? gf_hub_block_of_row_floats(rw) : 0;
+}
+
+void gf_hub_decay(float eta, float regu, int B, float *hi, float *lo)
+{
+    const double a = 1.0 - (double)eta * (double)regu;
+    double p = 1.0;                                   // a^k by repeated DOUBLE multiplication: k <= 32 roundings of 2^-53 each
+    for (int k = 0; k <= B; ++k) {
+        hi[k] = (float)p;
+        lo[k] = (float)(p - (double)hi[k]);
+        p *= a;
+    }
+}
+
 }  // namespace gemhip

@@ -66,4 +66,19 @@ std::vector<GfSeg> gf_units_segments(const std::vector<int64_t> &level_off, int 
 // rows per wavefront of the sweep launch over `nrows` rows of a level whose longest non-hub row has `maxlen` firing edges; forced > 0 overrides
 int gf_level_rows_per_wave(int forced, int64_t maxlen, int64_t nrows, int kmax);
 
+// ---- blocked hub rows (gf_hub_block_kernel, gemhip_gf_plan_set_hub_block): B edges of a hub row are applied with one Gram matrix of their neighbour
+// rows, B scalar steps and one GEMV instead of B dependent dot-and-axpy steps.
+constexpr int GF_HUB_BLOCK_MAX = 32;
+// floats of a row as the kernels stage it: a lane holds 2 floats (even d) or 1 (odd d) of each of 1, 2, 4 or 8 64-lane chunks; 0 = d unsupported
+int gf_row_floats(int d);
+// B for a staged row of `row_floats` floats: one 32x32 fp32 MFMA tile while B rows, their Gram matrix and a ring of such stages fit a CU's LDS,
+// one 16x16 tile for the wide rows
+constexpr int gf_hub_block_of_row_floats(int row_floats) { return row_floats <= 256 ? 32 : 16; }
+// B for width d (0 = d unsupported)
+int gf_hub_block(int d);
+// hi[k] = fl32(a^k), lo[k] = fl32(a^k - hi[k]) for k = 0..B, a = 1 - (double)eta * (double)regu and its powers evaluated in double: the decay a block
+// applies to the row and to the earlier steps of the block.  (Repeated fp32 multiplication by fl32(a) carries fl32(a)'s representation error into
+// every step, systematically: DESIGN.md "GF: blocked hub rows".)
+void gf_hub_decay(float eta, float regu, int B, float *hi, float *lo);
+
 }  // namespace gemhip

@@ -37,6 +37,11 @@ training something else.  Two opt-ins:
     is a single-device schedule: with n_gpus > 1 a list that needs it raises ValueError before any device call.
   * `regroup_edges=True` regroups the list by source (first-appearance order; gem_amd.graph.group_edges_by_source) -- fast, but a
     different visiting order than the reference's for that file.
+
+`hub_block=True` runs the hub rows of a power-law graph (rows with at least GEMHIP_GF_HUB_EDGES firing edges, default 1024) B edges at a time through a
+Gram matrix on the matrix units (gemhip_gf_plan_set_hub_block, DESIGN.md "GF: blocked hub rows"): the same updates within the fp32 tolerance of the
+sequential loop, not bit-identical to the default schedule.  `self._stats` records 'hub_block' (the B in effect) and 'hub_rows'.  A single-GPU
+kwarg: with n_gpus > 1 it raises ValueError before any device call (GEMHIP_GF_HUB_BLOCK=1 in the environment reaches the plans of every rank).
 """
 import ctypes as C
 
@@ -72,6 +77,12 @@ class GraphFactorization(StaticGraphEmbedding):
             if _multi.resolve(self)[0] != 'single' and not row_schedule_represents(src, dst):
                 raise ValueError('exact_edge_order=True: this edge order needs the unit schedule, which is a single-device schedule; '
                                  'n_gpus=%r (train on one GPU, or regroup_edges=True if the reordering is acceptable)' % (getattr(self, '_n_gpus', 1),))
+        hub_block = bool(getattr(self, '_hub_block', False))
+        if hub_block:
+            from gem_amd.embedding import _multi
+            if _multi.resolve(self)[0] != 'single':
+                raise ValueError('hub_block=True is a switch of the single-GPU plan; n_gpus=%r (set GEMHIP_GF_HUB_BLOCK=1 in the environment: every '
+                                 'rank\'s plan reads it at creation)' % (getattr(self, '_n_gpus', 1),))
         t_ingested = time.perf_counter()
         d = int(self._d)
         self._node_num = n
@@ -101,7 +112,7 @@ class GraphFactorization(StaticGraphEmbedding):
         device_init = getattr(self, '_device_init', None)
         if device_init is None:
             device_init = seed is not None
-        if device_init or verbose or exact:
+        if device_init or verbose or exact or hub_block:
             X0 = np.empty((n, d), dtype=np.float32)
             plan = C.c_void_p()
             info = (C.c_int64 * 8)()
@@ -114,6 +125,8 @@ class GraphFactorization(StaticGraphEmbedding):
                                                    _hip.ptr(wf, C.c_float), d, 0, n, C.byref(plan)))
             t_plan = time.perf_counter()
             try:
+                if hub_block:
+                    _hip.check(L.gemhip_gf_plan_set_hub_block(plan, 1))
                 if device_init:
                     _hip.check(L.gemhip_gf_plan_init_embedding(plan, int(seed if seed is not None else np.random.randint(2 ** 31 - 1)), 0.01))
                 else:
@@ -122,6 +135,9 @@ class GraphFactorization(StaticGraphEmbedding):
                     _hip.check(L.gemhip_gf_plan_set_embedding(plan, _hip.ptr(X0, C.c_float)))
                 t_init = time.perf_counter()
                 _hip.check(L.gemhip_gf_plan_info(plan, info))
+                hub = (C.c_int32(0), C.c_int64(0))
+                if hub_block:
+                    _hip.check(L.gemhip_gf_plan_hub_block(plan, C.byref(hub[0]), C.byref(hub[1])))
                 el, done, max_iter = 0.0, 0, int(self._max_iter)
                 step = max(1, int(getattr(self, '_print_step', 10000))) if verbose else max(1, max_iter)
                 self._objective_log = []
@@ -150,6 +166,8 @@ class GraphFactorization(StaticGraphEmbedding):
             self._stats = {'kernel_seconds': el, 'updates_per_sweep': info[0], 'rows_per_sweep': info[1], 'levels': info[2]}
             if exact:
                 self._stats.update({'schedule': 'units' if info[7] else 'rows', 'units': info[1]})
+            if hub_block:
+                self._stats.update({'hub_block': hub[0].value, 'hub_rows': hub[1].value})
             self._X = X0.astype(np.float64)
             t_end = time.perf_counter()
             # the breakdown of _hip.api_wall, stamped here: the staged calls are not one-shot drop-ins, gemhip_last_call_phases does not cover them

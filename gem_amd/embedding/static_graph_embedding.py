@@ -22,7 +22,7 @@ import numpy as np
 class StaticGraphEmbedding(object):
     hyper_params = {}
     backend_params = ('seed', 'device_init', 'flags', 'tol', 'oversample', 'krylov_steps', 'max_restarts', 'regroup_edges', 'exact_edge_order', 'verbose',
-                      'n_gpus', 'devices', 'virtual_ranks', 'episodes')
+                      'n_gpus', 'devices', 'virtual_ranks', 'episodes', 'hub_block')
 
     def __init__(self, *args, **kwargs):
         self._method_name = None

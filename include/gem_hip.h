@@ -113,6 +113,17 @@ int gemhip_gf_plan_set_rows_per_wave(gemhip_gf_plan_t plan, int32_t rows_per_wav
  * (default: one launch per sweep and level), k > 1 = up to k sweeps per launch on single-level plans without hub rows (others keep the launch loop);
  * max_grid caps the workgroups of that launch (0 = what the occupancy allows).  Bit-identical tables either way.  No reference counterpart. */
 int gemhip_gf_plan_set_fused_sweeps(gemhip_gf_plan_t plan, int32_t sweeps_per_launch, int32_t max_grid);
+/* Blocked hub rows: 0 = off (default), 1 = on; anything else is GEMHIP_E_INVALID.  On, the rows the plan marks as hub rows (GEMHIP_GF_HUB_EDGES
+ * firing edges or more, default 1024) apply their edges B at a time -- one Gram matrix of the B neighbour rows on the fp32 matrix units, B scalar
+ * steps, one GEMV -- instead of B dependent dot-and-axpy steps (gf_hub_block_kernel; DESIGN.md "GF: blocked hub rows").  NOT bit-identical to the row
+ * kernels: the same updates in another association of the same fp32 operations.  The bound it meets is the one the row kernels meet: every entry
+ * within 2e-5 of max|X| of the sequential fp32 loop of gf.cpp:152-164 (tests/test_gf_hub_block_gpu.py).  Deterministic: a row's result depends only on
+ * its edge list and inputs.  All other rows are computed exactly as with the switch off.  No effect on plans without hub rows; accepted without
+ * effect on a unit plan.  GEMHIP_GF_HUB_BLOCK=1 in the environment sets the initial value of every plan at its creation (so it reaches
+ * gemhip_gf_train and gemhip_gf_train_multi).  No reference counterpart. */
+int gemhip_gf_plan_set_hub_block(gemhip_gf_plan_t plan, int32_t on);
+/* block = the B in effect (0 when the switch is off, and on a unit plan), hub_rows = the hub rows of the plan (all levels). */
+int gemhip_gf_plan_hub_block(gemhip_gf_plan_t plan, int32_t *block, int64_t *hub_rows);
 int gemhip_gf_plan_get_embedding(gemhip_gf_plan_t plan, float *X_host);
 /* Device pointer of the CURRENT table (the one holding the latest sweep). */
 int gemhip_gf_plan_current(gemhip_gf_plan_t plan, void **dX);
