@@ -1171,6 +1171,10 @@ extern "C" int gemhip_gf_objective(int64_t n, int64_t m, const int32_t *src, con
                                    const float *X_host, double *out)
 {
     GEMHIP_REQUIRE(n > 0 && m >= 0 && d >= 1 && X_host && out, "gf_objective: bad arguments");
+    GEMHIP_REQUIRE(m == 0 || (src && dst), "gf_objective: bad edge arrays");
+    for (int64_t e = 0; e < m; ++e)                          // the kernel reads rows src[e], dst[e] of X unchecked
+        GEMHIP_REQUIRE(src[e] >= 0 && src[e] < n && dst[e] >= 0 && dst[e] < n, "gf_objective: edge %lld = (%d,%d) outside [0,%lld)", (long long)e, src[e],
+                       dst[e], (long long)n);
     DevBuf<int32_t> ds, dd; DevBuf<float> dw, dX; DevBuf<double> dout;
     GEMHIP_CHECK(ds.upload(src, m));
     GEMHIP_CHECK(dd.upload(dst, m));

@@ -152,7 +152,8 @@ int gemhip_gf_plan_set_fused_levels(gemhip_gf_plan_t plan, int32_t max_units);
 int gemhip_gf_any_order_schedule(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, int32_t *unit_out, int32_t *level_out,
                                  int32_t *flags_out, int64_t *counts);
 /* gf.cpp:94-113 objective on the device table: out = {f1, f2}. `m` edges as in
- * plan_create but over ALL edges (no dst>src filter), like the reference. */
+ * plan_create but over ALL edges (no dst>src filter), like the reference.  An edge outside [0, n), or m > 0 with a NULL src or dst, is
+ * GEMHIP_E_INVALID before any device call (the first offender is named as gemhip_gf_train names it). */
 int gemhip_gf_objective(int64_t n, int64_t m, const int32_t *src,
                         const int32_t *dst, const float *w, int32_t d,
                         const float *X_host, double *out);

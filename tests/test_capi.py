@@ -244,3 +244,36 @@ def test_operator_entry_points_reject_a_bad_csr_before_any_device_call():
             rc = fn(n, nnz, _hip.ptr(rp, C.c_int64), _hip.ptr(col, C.c_int32), None, 1, 0, 2, 1, 1e-6, 1, _hip.ptr(V, C.c_float), _hip.ptr(s, C.c_float), None)
             assert rc == _hip.E_INVALID
             assert L.gemhip_last_error() == msg % who
+
+
+def test_gf_objective_rejects_a_bad_edge_list_before_any_device_call():
+    """gf_objective_kernel reads rows src[e] and dst[e] of X unchecked, so gemhip_gf_objective refuses on the host what gemhip_gf_train refuses: an
+    endpoint outside [0, n), in the same words and naming the FIRST offender, and m > 0 with a NULL src or dst.  Validation only -- the calls return
+    before their first HIP call, so this runs without a GPU."""
+    import ctypes as C
+    import numpy as np
+    L = _hip.lib()
+    n, d = 5, 3
+    X = np.ones((n, d), np.float32)
+    out = (C.c_double * 2)(-7.0, -7.0)
+
+    def call(src, dst, m=None):
+        src = None if src is None else np.array(src, np.int32); dst = None if dst is None else np.array(dst, np.int32)
+        m = m if m is not None else len(src)
+        return L.gemhip_gf_objective(n, m, _hip.ptr(src, C.c_int32), _hip.ptr(dst, C.c_int32), None, d, _hip.ptr(X, C.c_float), out)
+
+    for src, dst, msg in (([0, 1, 2, 9], [1, 5, 2, 0], b'gf_objective: edge 1 = (1,5) outside [0,5)'),        # dst == n; a later edge is worse
+                          ([0, 4, 5], [1, 4, 0], b'gf_objective: edge 2 = (5,0) outside [0,5)'),              # src == n (the self-loop (4,4) is fine)
+                          ([0, -1], [1, 2], b'gf_objective: edge 1 = (-1,2) outside [0,5)'),
+                          ([0, 1], [1, -2147483648], b'gf_objective: edge 1 = (1,-2147483648) outside [0,5)')):
+        assert call(src, dst) == _hip.E_INVALID
+        assert L.gemhip_last_error() == msg
+    for src, dst in ((None, [1, 2]), ([1, 2], None), (None, None)):
+        assert call(src, dst, m=2) == _hip.E_INVALID
+        assert L.gemhip_last_error() == b'gf_objective: bad edge arrays'
+    assert call([0], [1], m=-1) == _hip.E_INVALID
+    assert (out[0], out[1]) == (-7.0, -7.0)                            # nothing was written
+    # gemhip_gf_train's wording for the same mistake (its planner refuses before any device call too)
+    src = np.array([0, 1], np.int32); dst = np.array([1, 5], np.int32)
+    assert L.gemhip_gf_train(n, 2, _hip.ptr(src, C.c_int32), _hip.ptr(dst, C.c_int32), None, d, 0.1, 0.1, 1, _hip.ptr(X, C.c_float), None) == _hip.E_INVALID
+    assert L.gemhip_last_error().split(b': ', 1)[1] == b'edge 1 = (1,5) outside [0,5)'

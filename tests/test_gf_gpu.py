@@ -107,6 +107,11 @@ def test_objective_kernel(sbm1024):
                                               _hip.ptr(w, C.c_float), 128, _hip.ptr(X, C.c_float), out))
     f1, f2 = oracle.gf_objective(n, src, dst, w, 128, X)
     assert out[0] == pytest.approx(f1, rel=1e-5) and out[1] == pytest.approx(f2, rel=1e-5)
+    # ... and inside the derived bound (instrument_refs.py; every other shape: test_gf_objective_gpu.py)
+    import instrument_refs as ir
+    _, _, b1, b2 = ir.gf_reference_and_bound(n, src, dst, w, 128, X)
+    print('GF objective SBM-1024 d=128: |f1 - oracle| / bound = %.3g (bound / f1 = %.2g), |f2 - oracle| / bound = %.3g' % (abs(out[0] - f1) / b1, b1 / f1, abs(out[1] - f2) / b2))
+    assert abs(out[0] - f1) <= b1 and abs(out[1] - f2) <= b2
 
 
 def test_class_api_and_map_parity(karate, sbm1024):
