@@ -16,7 +16,12 @@
 // Test mode: a device list with REPEATED entries (e.g. {0, 0, 0, 0}) runs the ranks as VIRTUAL ranks on one device -- RCCL refuses two ranks on one
 // GPU, so the three collectives are then plain device-to-device copies on one stream; everything else (sharding, episode table, bucket order, ring)
 // is the production code.  That is how the one-GPU test box checks N > 1 (tests/test_multi_capi_gpu.py).
+//
+// What the two drivers compute before and between their device steps -- shards, row blocks, the edge orders GF can shard, the episode table, alpha's
+// token offsets, the cut and paste of a table partition -- is host arithmetic in multi_plan.hip (no HIP; tests/test_multi_plan.py holds it against
+// gem_amd/multi_gpu.py on the CPU).  This file words the refusals and issues the device steps over such a plan.
 #include "common.hpp"
+#include "multi_plan.hpp"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <vector>
@@ -104,7 +109,12 @@ __global__ void add_i32_kernel(int32_t *__restrict__ acc, const int32_t *__restr
     if (i < n) acc[i] += x[i];
 }
 
-// The ranks of one call: devices, one stream per rank, and the three collectives the schedules need.
+// a step of an entry point that returns the library's own code
+#define GEMHIP_TRY(x) do { if (int _rc = (x)) return _rc; } while (0)
+
+// The ranks of one call: devices, one stream per rank, and the three collectives the schedules need.  Owns the communicators and the streams.  An
+// entry point declares its device buffers BEFORE the fabric and its per-rank handles AFTER it, so that on every way out the handles go first, then
+// the communicators, then every stream is drained and destroyed on its own device and the caller's device restored, and only then the buffers are freed.
 struct Fabric {
     int N = 0;
     bool virt = false;                       // repeated devices: virtual ranks on one stream, copies instead of RCCL
@@ -113,6 +123,17 @@ struct Fabric {
     std::vector<hipStream_t> st;
     std::vector<ncclComm_t> comm;
     int prev_dev = 0;
+
+    Fabric() = default;
+    Fabric(const Fabric &) = delete;
+    Fabric &operator=(const Fabric &) = delete;
+    ~Fabric()
+    {
+        for (int r = 0; r < (int)comm.size(); ++r) if (comm[r]) rccl().CommDestroy(comm[r]);
+        for (int r = 0; r < (virt ? std::min(N, 1) : N); ++r)
+            if (r < (int)st.size() && st[r]) { (void)hipSetDevice(dev[r]); (void)hipStreamSynchronize(st[r]); (void)hipStreamDestroy(st[r]); }
+        (void)hipSetDevice(prev_dev);
+    }
 
     int init(int32_t n_gpus, const int32_t *devices)
     {
@@ -151,20 +172,11 @@ struct Fabric {
     int use(int r) { GEMHIP_CHECK(hipSetDevice(dev[r])); return GEMHIP_OK; }
     int sync_all()
     {
-        // the DEVICE, not only the rank's stream: the streams are non-blocking, i.e. not ordered with the null stream, and the set-up phases use null-stream
-        // hipMemcpy (device to device) / hipMemset, which return before they complete.  With a stream-only wait here the first sweep on st[r] could run
-        // while the copy Xb <- Xa of gemhip_gf_train_multi was still in flight and have its rows overwritten (seen ONCE, round 6, in the closing tier:
-        // gemhip_gf_train_multi on one rank differed from gemhip_gf_train; the same hole existed for the zeroed SynNeg partitions of the node2vec driver).
+        // the DEVICE, not only the rank's stream: the streams are non-blocking, i.e. not ordered with the null stream, which the library calls between
+        // the phases use for their own set-up (gemhip_sgns_init, the unigram builders, the blocking uploads).  The drivers' own device-side copies and
+        // memsets are issued on st[r], so their order with the kernels does not rest on this wait.
         for (int r = 0; r < (virt ? 1 : N); ++r) { GEMHIP_CHECK(hipSetDevice(dev[r])); GEMHIP_CHECK(hipStreamSynchronize(st[r])); GEMHIP_CHECK(hipDeviceSynchronize()); }
         return GEMHIP_OK;
-    }
-    void destroy()
-    {
-        for (int r = 0; r < (int)comm.size(); ++r) if (comm[r]) rccl().CommDestroy(comm[r]);
-        comm.clear();
-        for (int r = 0; r < (virt ? std::min(N, 1) : N); ++r) if (r < (int)st.size() && st[r]) { hipSetDevice(dev[r]); hipStreamSynchronize(st[r]); hipStreamDestroy(st[r]); }
-        st.clear();
-        hipSetDevice(prev_dev);
     }
     // every rank's buf holds N blocks of `bytes`; block r of rank r is valid on entry, all blocks on every rank on exit
     int all_gather_inplace(const std::vector<void *> &buf, size_t bytes)
@@ -216,6 +228,19 @@ struct Fabric {
     }
 };
 
+// One rank's library handle (a GF plan, a node2vec handle): move-only, released on the rank's device.
+template <typename H, int (*DESTROY)(H)>
+struct RankHandle {
+    H h = nullptr;
+    int dev = 0;
+    RankHandle() = default;
+    RankHandle(RankHandle &&o) noexcept : h(o.h), dev(o.dev) { o.h = nullptr; }
+    RankHandle &operator=(RankHandle &&o) noexcept { std::swap(h, o.h); std::swap(dev, o.dev); return *this; }
+    ~RankHandle() { if (h) { (void)hipSetDevice(dev); DESTROY(h); } }
+};
+using RankGfPlan = RankHandle<gemhip_gf_plan_t, gemhip_gf_plan_destroy>;
+using RankN2v = RankHandle<gemhip_n2v_t, gemhip_n2v_destroy>;
+
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 using Bytes = DevBuf<char>;
@@ -229,49 +254,48 @@ extern "C" int gemhip_rccl_selftest(int32_t n_gpus, const int32_t *devices, int6
 {
     GEMHIP_REQUIRE(bytes >= 4 && bytes % 4 == 0 && bytes <= ((int64_t)1 << 30), "rccl_selftest: bytes=%lld (multiple of 4, <= 1 GiB)", (long long)bytes);
     GEMHIP_REQUIRE(n_gpus >= 1 && n_gpus <= 64, "rccl_selftest: n_gpus=%d (1..64)", n_gpus);
-    Fabric F;
-    F.always_rccl = true;                    // n_gpus = 1 exercises RCCL itself: a 1-rank all-gather / all-reduce / self send-recv
-    int rc = F.init(n_gpus, devices);
     const int N = n_gpus;
     const int64_t words = bytes / 4;
     std::vector<Bytes> G(N), A(N), S(N), Rv(N);
+    Fabric F;
+    F.always_rccl = true;                    // n_gpus = 1 exercises RCCL itself: a 1-rank all-gather / all-reduce / self send-recv
+    GEMHIP_TRY(F.init(n_gpus, devices));
     std::vector<void *> g(N), s(N), rv(N);
     std::vector<int32_t *> a(N);
     const double t0 = now_s();
-    for (int r = 0; r < N && !rc; ++r) {
-        if (!rc) rc = alloc_on(G[r], F.dev[r], (size_t)bytes * N);
-        if (!rc) rc = alloc_on(A[r], F.dev[r], (size_t)bytes);
-        if (!rc) rc = alloc_on(S[r], F.dev[r], (size_t)bytes);
-        if (!rc) rc = alloc_on(Rv[r], F.dev[r], (size_t)bytes);
-        if (rc) break;
+    for (int r = 0; r < N; ++r) {
+        GEMHIP_TRY(alloc_on(G[r], F.dev[r], (size_t)bytes * N));
+        GEMHIP_TRY(alloc_on(A[r], F.dev[r], (size_t)bytes));
+        GEMHIP_TRY(alloc_on(S[r], F.dev[r], (size_t)bytes));
+        GEMHIP_TRY(alloc_on(Rv[r], F.dev[r], (size_t)bytes));
         g[r] = G[r].get(); a[r] = (int32_t *)A[r].get(); s[r] = S[r].get(); rv[r] = Rv[r].get();
         std::vector<int32_t> h((size_t)words * N, -1), hb((size_t)words);
         for (int64_t i = 0; i < words; ++i) { h[(size_t)r * words + i] = (int32_t)(1000003 * r + i); hb[i] = (int32_t)((r + 1) * (i % 97 + 1)); }
         if (hipMemcpy(g[r], h.data(), (size_t)bytes * N, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(a[r], hb.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(s[r], hb.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(GEMHIP_E_HIP, "rccl_selftest: upload failed");
+            return fail(GEMHIP_E_HIP, "rccl_selftest: upload failed");
     }
-    if (!rc) rc = F.all_gather_inplace(g, (size_t)bytes);
-    if (!rc) rc = F.all_reduce_sum_i32(a, words);
-    if (!rc) rc = F.ring_shift(s, rv, (size_t)bytes);
-    if (!rc) rc = F.sync_all();
-    for (int r = 0; r < N && !rc; ++r) {
+    GEMHIP_TRY(F.all_gather_inplace(g, (size_t)bytes));
+    GEMHIP_TRY(F.all_reduce_sum_i32(a, words));
+    GEMHIP_TRY(F.ring_shift(s, rv, (size_t)bytes));
+    GEMHIP_TRY(F.sync_all());
+    for (int r = 0; r < N; ++r) {
         std::vector<int32_t> h((size_t)words * N), ha((size_t)words), hr((size_t)words);
-        hipSetDevice(F.dev[r]);
+        GEMHIP_TRY(F.use(r));
         if (hipMemcpy(h.data(), g[r], (size_t)bytes * N, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ha.data(), a[r], bytes, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(hr.data(), rv[r], bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GEMHIP_E_HIP, "rccl_selftest: download failed"); break; }
-        for (int q = 0; q < N && !rc; ++q)
+            hipMemcpy(hr.data(), rv[r], bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(GEMHIP_E_HIP, "rccl_selftest: download failed");
+        for (int q = 0; q < N; ++q)
             for (int64_t i = 0; i < words; ++i)
-                if (h[(size_t)q * words + i] != (int32_t)(1000003 * q + i)) { rc = fail(GEMHIP_E_HIP, "rccl_selftest: all-gather: rank %d block %d word %lld wrong", r, q, (long long)i); break; }
+                if (h[(size_t)q * words + i] != (int32_t)(1000003 * q + i)) return fail(GEMHIP_E_HIP, "rccl_selftest: all-gather: rank %d block %d word %lld wrong", r, q, (long long)i);
         const int64_t tri = (int64_t)N * (N + 1) / 2;
-        for (int64_t i = 0; i < words && !rc; ++i) {
-            if (ha[i] != (int32_t)(tri * (i % 97 + 1))) rc = fail(GEMHIP_E_HIP, "rccl_selftest: all-reduce: rank %d word %lld wrong", r, (long long)i);
-            else if (hr[i] != (int32_t)(((r + 1) % N + 1) * (i % 97 + 1))) rc = fail(GEMHIP_E_HIP, "rccl_selftest: ring shift: rank %d word %lld wrong", r, (long long)i);
+        for (int64_t i = 0; i < words; ++i) {
+            if (ha[i] != (int32_t)(tri * (i % 97 + 1))) return fail(GEMHIP_E_HIP, "rccl_selftest: all-reduce: rank %d word %lld wrong", r, (long long)i);
+            if (hr[i] != (int32_t)(((r + 1) % N + 1) * (i % 97 + 1))) return fail(GEMHIP_E_HIP, "rccl_selftest: ring shift: rank %d word %lld wrong", r, (long long)i);
         }
     }
     if (seconds) *seconds = now_s() - t0;
-    F.destroy();
-    return rc;
+    return GEMHIP_OK;
 }
 
 // gf.py:81-101 on n_gpus devices.  stats (optional, 8 doubles): {seconds of the sweeps incl. exchanges (wall, all ranks synchronised), updates per
@@ -281,71 +305,61 @@ extern "C" int gemhip_gf_train_multi(int64_t n, int64_t m, const int32_t *src, c
 {
     GEMHIP_REQUIRE(X_inout != nullptr && max_iter >= 0 && n > 0 && m >= 0 && d >= 1, "gf_train_multi: bad arguments");
     GEMHIP_REQUIRE(n_gpus >= 1 && n_gpus <= 64, "gf_train_multi: n_gpus=%d (1..64)", n_gpus);          // before anything is sized or divided by it
-    if (n_gpus > 1) {
-        // ranks read each other's rows from the PREVIOUS sweep's table: that is the reference's sweep only when no firing edge reads a row the
-        // reference has already updated in the same sweep, i.e. when the firing sources are first visited in ascending id order (gf.py:93-100 over
-        // graph.edges() of a graph whose nodes were inserted in id order -- every call site of the reference); other orders need one GPU
-        int64_t last = -1;
-        std::vector<char> seen((size_t)n, 0);
-        for (int64_t e = 0; e < m; ++e) {
-            GEMHIP_REQUIRE(src[e] >= 0 && src[e] < n && dst[e] >= 0 && dst[e] < n, "gf_train_multi: edge %lld out of range", (long long)e);
-            if (dst[e] > src[e] && !seen[src[e]]) {
-                seen[src[e]] = 1;
-                if (src[e] < last) return fail(GEMHIP_E_UNSUPPORTED, "gf_train_multi: firing sources are not first visited in ascending id order (row %d after row %lld): "
-                                                                     "sharding by source row would change the reference's Gauss-Seidel order; use n_gpus = 1", src[e], (long long)last);
-                last = src[e];
-            }
-        }
+    if (n_gpus > 1) {                        // other edge orders need one GPU (the rule: multi_plan.hpp)
+        const GfShardError e = gf_check_shardable(n, m, src, dst);
+        GEMHIP_REQUIRE(e.kind != GfShardError::EDGE_OUT_OF_RANGE, "gf_train_multi: edge %lld out of range", (long long)e.edge);
+        if (e) return fail(GEMHIP_E_UNSUPPORTED, "gf_train_multi: firing sources are not first visited in ascending id order (row %d after row %lld): "
+                                                 "sharding by source row would change the reference's Gauss-Seidel order; use n_gpus = 1", (int)e.row, (long long)e.after);
     }
-    Fabric F;
-    int rc = F.init(n_gpus, devices);
     const int N = n_gpus;
-    const int64_t block = (n + N - 1) / N, n_pad = block * N;
-    std::vector<gemhip_gf_plan_t> plan(N, nullptr);
+    const GfRowBlocks B = gf_row_blocks(n, N);
+    const size_t table_bytes = (size_t)B.n_pad * d * sizeof(float), block_bytes = (size_t)B.block * d * sizeof(float);
     std::vector<Bytes> Xa(N), Xb(N);
+    Fabric F;
+    GEMHIP_TRY(F.init(n_gpus, devices));
+    std::vector<RankGfPlan> plan(N);
     std::vector<float> Xpad;
-    if (!rc && n_pad != n) { Xpad.assign((size_t)n_pad * d, 0.f); std::memcpy(Xpad.data(), X_inout, (size_t)n * d * sizeof(float)); }
-    const float *Xsrc = n_pad != n ? Xpad.data() : X_inout;
+    if (B.n_pad != n) { Xpad.assign((size_t)B.n_pad * d, 0.f); std::memcpy(Xpad.data(), X_inout, (size_t)n * d * sizeof(float)); }
+    const float *Xsrc = B.n_pad != n ? Xpad.data() : X_inout;
     double upd = 0, rows = 0;
-    for (int r = 0; r < N && !rc; ++r) {
-        rc = F.use(r);
-        const int64_t r0 = std::min<int64_t>(r * block, n), r1 = std::min<int64_t>((r + 1) * block, n);
-        if (!rc) rc = gemhip_gf_plan_create(n, m, src, dst, w, d, r0, r1, &plan[r]);
-        if (!rc) rc = alloc_on(Xa[r], F.dev[r], (size_t)n_pad * d * sizeof(float));
-        if (!rc) rc = alloc_on(Xb[r], F.dev[r], (size_t)n_pad * d * sizeof(float));
-        if (!rc && (hipMemcpy(Xa[r].get(), Xsrc, (size_t)n_pad * d * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(Xb[r].get(), Xa[r].get(), (size_t)n_pad * d * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess))
-            rc = fail(GEMHIP_E_HIP, "gf_train_multi: table upload failed on rank %d", r);
-        if (!rc) rc = gemhip_gf_plan_bind(plan[r], Xa[r].get(), Xb[r].get());
+    for (int r = 0; r < N; ++r) {
+        const Range own = B.rows(r);
+        GEMHIP_TRY(F.use(r));
+        plan[r].dev = F.dev[r];
+        GEMHIP_TRY(gemhip_gf_plan_create(n, m, src, dst, w, d, own.lo, own.hi, &plan[r].h));
+        GEMHIP_TRY(alloc_on(Xa[r], F.dev[r], table_bytes));
+        GEMHIP_TRY(alloc_on(Xb[r], F.dev[r], table_bytes));
+        // the upload is complete when it returns (pageable host memory); the copy Xb <- Xa is ordered with the sweeps by the rank's stream
+        if (hipMemcpy(Xa[r].get(), Xsrc, table_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpyAsync(Xb[r].get(), Xa[r].get(), table_bytes, hipMemcpyDeviceToDevice, F.st[r]) != hipSuccess)
+            return fail(GEMHIP_E_HIP, "gf_train_multi: table upload failed on rank %d", r);
+        GEMHIP_TRY(gemhip_gf_plan_bind(plan[r].h, Xa[r].get(), Xb[r].get()));
         int64_t info[8];
-        if (!rc) { rc = gemhip_gf_plan_info(plan[r], info); upd += (double)info[0]; rows += (double)info[1]; }
+        GEMHIP_TRY(gemhip_gf_plan_info(plan[r].h, info));
+        upd += (double)info[0]; rows += (double)info[1];
     }
-    if (!rc) rc = F.sync_all();
+    GEMHIP_TRY(F.sync_all());
     const double t0 = now_s();
     std::vector<void *> cur(N);
-    for (int it = 0; it < max_iter && !rc; ++it) {
-        for (int r = 0; r < N && !rc; ++r) {
-            rc = F.use(r);
-            if (!rc) rc = gemhip_gf_plan_sweeps(plan[r], 1, eta, regu, F.st[r]);
-            if (!rc) rc = gemhip_gf_plan_current(plan[r], &cur[r]);
+    for (int it = 0; it < max_iter; ++it) {
+        for (int r = 0; r < N; ++r) {
+            GEMHIP_TRY(F.use(r));
+            GEMHIP_TRY(gemhip_gf_plan_sweeps(plan[r].h, 1, eta, regu, F.st[r]));
+            GEMHIP_TRY(gemhip_gf_plan_current(plan[r].h, &cur[r]));
         }
-        if (!rc) rc = F.all_gather_inplace(cur, (size_t)block * d * sizeof(float));          // owned row blocks -> every rank holds the whole new table
+        GEMHIP_TRY(F.all_gather_inplace(cur, block_bytes));          // owned row blocks -> every rank holds the whole new table
     }
-    if (!rc) rc = F.sync_all();
+    GEMHIP_TRY(F.sync_all());
     const double el = now_s() - t0;
-    if (!rc) {
-        void *p0 = nullptr;
-        rc = F.use(0);
-        if (!rc) rc = gemhip_gf_plan_current(plan[0], &p0);
-        if (!rc && hipMemcpy(X_inout, p0, (size_t)n * d * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(GEMHIP_E_HIP, "gf_train_multi: download failed");
-    }
-    if (!rc && stats) {
-        stats[0] = el; stats[1] = upd; stats[2] = rows; stats[3] = N > 1 ? (double)(N - 1) * block * d * 4.0 : 0.0; stats[4] = N; stats[5] = F.virt ? 1.0 : 0.0;
+    void *p0 = nullptr;
+    GEMHIP_TRY(F.use(0));
+    GEMHIP_TRY(gemhip_gf_plan_current(plan[0].h, &p0));
+    if (hipMemcpy(X_inout, p0, (size_t)n * d * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return fail(GEMHIP_E_HIP, "gf_train_multi: download failed");
+    if (stats) {
+        stats[0] = el; stats[1] = upd; stats[2] = rows; stats[3] = N > 1 ? (double)(N - 1) * B.block * d * 4.0 : 0.0; stats[4] = N; stats[5] = F.virt ? 1.0 : 0.0;
         stats[6] = 0.0; stats[7] = 0.0;
     }
-    for (int r = 0; r < N; ++r) if (plan[r]) { hipSetDevice(F.dev[r]); gemhip_gf_plan_destroy(plan[r]); }
-    F.destroy();
-    return rc;
+    return GEMHIP_OK;
 }
 
 // node2vec.py:27-54 on n_gpus devices (module comment).  `episodes` slices of every rank's walk shard (64 = the default of gem_amd/multi_gpu.py; the
@@ -357,134 +371,115 @@ extern "C" int gemhip_n2v_train_multi(int64_t n, int64_t nnz, const int64_t *row
 {
     GEMHIP_REQUIRE(X_out != nullptr && episodes >= 1 && epochs >= 1 && epochs < 256, "n2v_train_multi: bad arguments (episodes=%d epochs=%d)", episodes, epochs);
     GEMHIP_REQUIRE(n_gpus >= 1 && n_gpus <= 64, "n2v_train_multi: n_gpus=%d (1..64)", n_gpus);         // before anything is sized or divided by it
-    Fabric F;
-    int rc = F.init(n_gpus, devices);
     const int N = n_gpus;
-    std::vector<gemhip_n2v_t> h(N, nullptr);
-    for (int r = 0; r < N && !rc; ++r) { rc = F.use(r); if (!rc) rc = gemhip_n2v_create(n, nnz, row_ptr, col, w, &h[r]); }
+    std::vector<Bytes> corpus(N), segd(N), Pp(N), Na(N), Nb(N);
+    Fabric F;
+    GEMHIP_TRY(F.init(n_gpus, devices));
+    std::vector<RankN2v> h(N);
+    for (int r = 0; r < N; ++r) {
+        GEMHIP_TRY(F.use(r));
+        h[r].dev = F.dev[r];
+        GEMHIP_TRY(gemhip_n2v_create(n, nnz, row_ptr, col, w, &h[r].h));
+    }
     int64_t m_start = 0;
-    if (!rc) rc = gemhip_n2v_start_nodes(h[0], &m_start);
+    GEMHIP_TRY(gemhip_n2v_start_nodes(h[0].h, &m_start));
     const int64_t total = m_start * (int64_t)num_walks;
-    auto shard = [&](int r, int64_t &lo, int64_t &hi) { lo = total * r / N; hi = total * (r + 1) / N; };
+    const N2vMultiPlan P = n2v_multi_plan(total, N, episodes, walk_len, n, epochs);
     const double t0 = now_s();
     // ---- walks of my start-node shard, token counts summed over the ranks
     std::vector<int32_t *> cnt(N, nullptr);
-    for (int r = 0; r < N && !rc; ++r) {
-        int64_t lo, hi; shard(r, lo, hi);
-        rc = F.use(r);
-        if (!rc) rc = gemhip_n2v_walks(h[r], p, q, num_walks, walk_len, seed, flags, lo, hi, F.st[r]);
-        if (!rc) rc = gemhip_n2v_vocab(h[r], F.st[r]);
+    for (int r = 0; r < N; ++r) {
+        GEMHIP_TRY(F.use(r));
+        GEMHIP_TRY(gemhip_n2v_walks(h[r].h, p, q, num_walks, walk_len, seed, flags, P.shard[r].lo, P.shard[r].hi, F.st[r]));
+        GEMHIP_TRY(gemhip_n2v_vocab(h[r].h, F.st[r]));
         void *c = nullptr;
-        if (!rc) rc = gemhip_n2v_counts_ptr(h[r], &c);
+        GEMHIP_TRY(gemhip_n2v_counts_ptr(h[r].h, &c));
         cnt[r] = (int32_t *)c;
     }
-    if (!rc) rc = F.all_reduce_sum_i32(cnt, n);
-    if (!rc) rc = F.sync_all();
+    GEMHIP_TRY(F.all_reduce_sum_i32(cnt, n));
+    GEMHIP_TRY(F.sync_all());
     // ---- the walk corpus on every rank: shard r occupies rows [r * shard_rows, ...) (shorter shards padded with -1 tokens)
-    int64_t shard_rows = 1;
-    for (int r = 0; r < N; ++r) { int64_t lo, hi; shard(r, lo, hi); shard_rows = std::max(shard_rows, hi - lo); }
-    const size_t shard_bytes = (size_t)shard_rows * walk_len * sizeof(int32_t);
-    std::vector<Bytes> corpus(N), segd(N), Pp(N), Na(N), Nb(N);
+    const size_t shard_bytes = (size_t)P.shard_rows * walk_len * sizeof(int32_t);
     std::vector<void *> cptr(N);
-    for (int r = 0; r < N && !rc; ++r) {
-        int64_t lo, hi; shard(r, lo, hi);
-        rc = alloc_on(corpus[r], F.dev[r], shard_bytes * N);
-        if (!rc && hipMemsetAsync((char *)corpus[r].get() + (size_t)r * shard_bytes, 0xff, shard_bytes, F.st[r]) != hipSuccess) rc = fail(GEMHIP_E_HIP, "n2v_train_multi: memset");
-        if (!rc) rc = gemhip_n2v_copy_walks(h[r], 0, hi - lo, (char *)corpus[r].get() + (size_t)r * shard_bytes, F.st[r]);
+    for (int r = 0; r < N; ++r) {
+        GEMHIP_TRY(alloc_on(corpus[r], F.dev[r], shard_bytes * N));
+        char *mine = corpus[r].get() + (size_t)r * shard_bytes;
+        if (hipMemsetAsync(mine, 0xff, shard_bytes, F.st[r]) != hipSuccess) return fail(GEMHIP_E_HIP, "n2v_train_multi: memset");
+        GEMHIP_TRY(gemhip_n2v_copy_walks(h[r].h, 0, P.shard[r].hi - P.shard[r].lo, mine, F.st[r]));
         cptr[r] = corpus[r].get();
     }
-    if (!rc) rc = F.all_gather_inplace(cptr, shard_bytes);
+    GEMHIP_TRY(F.all_gather_inplace(cptr, shard_bytes));
     // ---- the per-partition unigram tables, in the layout the flags ask for: node-id order, or (GEMHIP_N2V_VOCAB_ORDER, the plugin default on one GPU)
     // the binary's -- each partition's nodes in order of first appearance in the WHOLE corpus, which every rank now holds
-    if (!rc) rc = F.sync_all();
-    for (int r = 0; r < N && !rc; ++r) {
-        rc = F.use(r);
-        if (!rc) rc = (flags & GEMHIP_N2V_VOCAB_ORDER) ? gemhip_n2v_build_unigram_parts_vocab_order(h[r], N, flags, corpus[r].get(), (int64_t)N * shard_rows * walk_len, nullptr, nullptr, nullptr, nullptr)
-                                                       : gemhip_n2v_build_unigram_parts(h[r], N, nullptr, nullptr);
+    GEMHIP_TRY(F.sync_all());
+    for (int r = 0; r < N; ++r) {
+        GEMHIP_TRY(F.use(r));
+        GEMHIP_TRY((flags & GEMHIP_N2V_VOCAB_ORDER) ? gemhip_n2v_build_unigram_parts_vocab_order(h[r].h, N, flags, corpus[r].get(), (int64_t)N * P.shard_rows * walk_len, nullptr, nullptr, nullptr, nullptr)
+                                                    : gemhip_n2v_build_unigram_parts(h[r].h, N, nullptr, nullptr));
     }
     // ---- LOCALLY HOT ROWS of the gathered corpus (nodes whose tokens are packed into few walks: the ends of isolated edges): never cached by the bucket launches
-    for (int r = 0; r < N && !rc; ++r) {
-        rc = F.use(r);
-        if (!rc) rc = gemhip_n2v_locally_hot_corpus(h[r], corpus[r].get(), (int64_t)N * shard_rows, walk_len, -1, nullptr, F.st[r]);
+    for (int r = 0; r < N; ++r) {
+        GEMHIP_TRY(F.use(r));
+        GEMHIP_TRY(gemhip_n2v_locally_hot_corpus(h[r].h, corpus[r].get(), (int64_t)N * P.shard_rows, walk_len, -1, nullptr, F.st[r]));
     }
-    // ---- episode table [episodes][3][N]: first row, walks present, first global walk id of every shard's slice; work items per shard = longest slice
-    std::vector<int64_t> tab((size_t)episodes * 3 * N), seg_len(episodes, 1);
-    for (int e = 0; e < episodes; ++e)
+    // ---- the episode table on every rank; InitPosEmb / InitNegEmb of the whole table a single GPU would draw, once (rank 0's device)
+    const size_t part_bytes = (size_t)P.prow * d * sizeof(float);
+    for (int r = 0; r < N; ++r) {
+        GEMHIP_TRY(alloc_on(segd[r], F.dev[r], P.tab.size() * sizeof(int64_t)));
+        if (hipMemcpy(segd[r].get(), P.tab.data(), P.tab.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return fail(GEMHIP_E_HIP, "n2v_train_multi: table upload");
+        if (r == 0) GEMHIP_TRY(gemhip_sgns_init(h[0].h, d, seed, nullptr, nullptr));
+        GEMHIP_TRY(alloc_on(Pp[r], F.dev[r], part_bytes));
+        GEMHIP_TRY(alloc_on(Na[r], F.dev[r], part_bytes));
+        GEMHIP_TRY(alloc_on(Nb[r], F.dev[r], part_bytes));
+    }
+    // ---- partition r of those tables: SynPos cut out of a host copy (the handle keeps its tables private; get_tables synchronises the device), SynNeg = 0
+    {
+        std::vector<float> full((size_t)n * d), part((size_t)P.prow * d);
+        GEMHIP_TRY(F.use(0));
+        GEMHIP_TRY(gemhip_sgns_get_tables(h[0].h, full.data(), nullptr));
         for (int r = 0; r < N; ++r) {
-            int64_t lo, hi; shard(r, lo, hi);
-            const int64_t a = (hi - lo) * e / episodes, z = (hi - lo) * (e + 1) / episodes;
-            int64_t *t = tab.data() + (size_t)e * 3 * N;
-            t[r] = r * shard_rows + a; t[N + r] = z - a; t[2 * N + r] = lo + a;
-            seg_len[e] = std::max(seg_len[e], z - a);
-        }
-    // ---- partition r of the initial tables a single GPU would draw (InitPosEmb / InitNegEmb): SynPos rows r, r + N, ...; SynNeg = 0
-    const int64_t prow = (n + N - 1) / N;
-    const size_t part_bytes = (size_t)prow * d * sizeof(float);
-    for (int r = 0; r < N && !rc; ++r) {
-        rc = F.use(r);
-        if (!rc) rc = alloc_on(segd[r], F.dev[r], tab.size() * sizeof(int64_t));
-        if (!rc && hipMemcpy(segd[r].get(), tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) rc = fail(GEMHIP_E_HIP, "n2v_train_multi: table upload");
-        if (!rc && r == 0) rc = gemhip_sgns_init(h[0], d, seed, nullptr, nullptr);       // InitPosEmb / InitNegEmb of the whole table, once (rank 0's device)
-        if (!rc) rc = alloc_on(Pp[r], F.dev[r], part_bytes);
-        if (!rc) rc = alloc_on(Na[r], F.dev[r], part_bytes);
-        if (!rc) rc = alloc_on(Nb[r], F.dev[r], part_bytes);
-    }
-    // the partitions are cut out of a host copy of that table (the handle keeps its tables private; get_tables synchronises the device)
-    if (!rc) {
-        std::vector<float> full((size_t)n * d), part((size_t)prow * d);
-        rc = F.use(0);
-        if (!rc) rc = gemhip_sgns_get_tables(h[0], full.data(), nullptr);
-        for (int r = 0; r < N && !rc; ++r) {
-            std::fill(part.begin(), part.end(), 0.f);
-            for (int64_t l = 0; l * N + r < n; ++l) std::memcpy(&part[(size_t)l * d], &full[(size_t)(l * N + r) * d], (size_t)d * sizeof(float));
-            hipSetDevice(F.dev[r]);
-            if (hipMemcpy(Pp[r].get(), part.data(), part_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemset(Na[r].get(), 0, part_bytes) != hipSuccess ||
-                hipMemset(Nb[r].get(), 0, part_bytes) != hipSuccess)
-                rc = fail(GEMHIP_E_HIP, "n2v_train_multi: partition upload failed on rank %d", r);
+            partition_cut(full.data(), n, d, r, N, part.data());
+            GEMHIP_TRY(F.use(r));
+            if (hipMemcpy(Pp[r].get(), part.data(), part_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemsetAsync(Na[r].get(), 0, part_bytes, F.st[r]) != hipSuccess ||
+                hipMemsetAsync(Nb[r].get(), 0, part_bytes, F.st[r]) != hipSuccess)
+                return fail(GEMHIP_E_HIP, "n2v_train_multi: partition upload failed on rank %d", r);
         }
     }
-    if (!rc) rc = F.sync_all();
+    GEMHIP_TRY(F.sync_all());
     const double t1 = now_s();
     // ---- episodes x rounds: bucket (r, (r + s) % N) on rank r, then the SynNeg partitions move one step around the ring
     std::vector<void *> ncur(N), ntmp(N);
     for (int r = 0; r < N; ++r) { ncur[r] = Na[r].get(); ntmp[r] = Nb[r].get(); }
-    int64_t alpha_total = 0;
-    for (int e = 0; e < episodes; ++e) alpha_total += seg_len[e] * N * walk_len;
-    alpha_total *= epochs;
-    int64_t done = 0, launches = 0;
-    for (int ep = 0; ep < epochs && !rc; ++ep)
-        for (int e = 0; e < episodes && !rc; ++e) {
-            for (int s = 0; s < N && !rc; ++s) {
-                for (int r = 0; r < N && !rc; ++r) {
-                    rc = F.use(r);
-                    if (!rc) rc = gemhip_sgns_train_part(h[r], corpus[r].get(), (int64_t)N * seg_len[e], walk_len, (const int64_t *)segd[r].get() + (size_t)e * 3 * N, N, seg_len[e], 0, window,
-                                                         0.025f, alpha_total, done, ep, seed, flags, r, (r + s) % N, Pp[r].get(), ncur[r], d, F.st[r]);
+    int64_t launches = 0;
+    for (int ep = 0; ep < epochs; ++ep)
+        for (int e = 0; e < episodes; ++e)
+            for (int s = 0; s < N; ++s) {
+                for (int r = 0; r < N; ++r) {
+                    GEMHIP_TRY(F.use(r));
+                    GEMHIP_TRY(gemhip_sgns_train_part(h[r].h, corpus[r].get(), (int64_t)N * P.seg_len[e], walk_len, (const int64_t *)segd[r].get() + (P.episode(e) - P.episode(0)), N,
+                                                      P.seg_len[e], 0, window, 0.025f, P.alpha_total, P.token_offset[(size_t)ep * episodes + e], ep, seed, flags, r, (r + s) % N,
+                                                      Pp[r].get(), ncur[r], d, F.st[r]));
                     ++launches;
                 }
-                if (!rc && N > 1) { rc = F.ring_shift(ncur, ntmp, part_bytes); std::swap(ncur, ntmp); }
+                if (N > 1) { GEMHIP_TRY(F.ring_shift(ncur, ntmp, part_bytes)); std::swap(ncur, ntmp); }
             }
-            done += seg_len[e] * N * walk_len;
-        }
-    if (!rc) rc = F.sync_all();
+    GEMHIP_TRY(F.sync_all());
     const double t2 = now_s();
-    // ---- row v of the result = partition v % N, local row v / N
+    // ---- the result: every partition pasted back into node-id order
     double pairs = 0;
-    if (!rc) {
-        std::vector<float> part((size_t)prow * d);
-        for (int r = 0; r < N && !rc; ++r) {
-            hipSetDevice(F.dev[r]);
-            if (hipMemcpy(part.data(), Pp[r].get(), part_bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(GEMHIP_E_HIP, "n2v_train_multi: download failed on rank %d", r); break; }
-            for (int64_t l = 0; l * N + r < n; ++l) std::memcpy(X_out + (size_t)(l * N + r) * d, &part[(size_t)l * d], (size_t)d * sizeof(float));
-            int64_t pr = 0;
-            rc = gemhip_sgns_pairs(h[r], &pr, 1);
-            pairs += (double)pr;
-        }
+    std::vector<float> part((size_t)P.prow * d);
+    for (int r = 0; r < N; ++r) {
+        GEMHIP_TRY(F.use(r));
+        if (hipMemcpy(part.data(), Pp[r].get(), part_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(GEMHIP_E_HIP, "n2v_train_multi: download failed on rank %d", r);
+        partition_paste(part.data(), n, d, r, N, X_out);
+        int64_t pr = 0;
+        GEMHIP_TRY(gemhip_sgns_pairs(h[r].h, &pr, 1));
+        pairs += (double)pr;
     }
-    if (!rc && stats) {
+    if (stats) {
         stats[0] = t1 - t0; stats[1] = t2 - t1; stats[2] = (double)total * walk_len; stats[3] = pairs; stats[4] = N > 1 ? (double)part_bytes : 0.0; stats[5] = N;
         stats[6] = F.virt ? 1.0 : 0.0; stats[7] = (double)launches / N;
     }
-    for (int r = 0; r < N; ++r) if (h[r]) { hipSetDevice(F.dev[r]); gemhip_n2v_destroy(h[r]); }
-    F.destroy();
-    return rc;
+    return GEMHIP_OK;
 }
+

@@ -324,7 +324,7 @@ class Node2VecPartitioned(object):
         its first walk -- plus the work items per shard (the longest slice) of every episode."""
         W = self.world
         shard = [shard_range(self.total_walks, r, W) for r in range(W)]
-        self.shard_rows = max(hi - lo for lo, hi in shard)             # rows per shard in the gathered corpus (shorter shards are padded)
+        self.shard_rows = max(1, max(hi - lo for lo, hi in shard))     # rows per shard in the gathered corpus (shorter shards are padded; never 0 rows)
         tab = np.zeros((self.episodes, 3, W), dtype=np.int64)
         seg_len = np.zeros(self.episodes, dtype=np.int64)
         for e in range(self.episodes):

@@ -52,6 +52,21 @@ def test_gf_train_multi_is_bit_identical_to_one_gpu(ranks):
     assert np.abs(b - ref).max() <= 2e-5 * np.abs(ref).max()
 
 
+@pytest.mark.parametrize('n', [4, 5, 3])
+def test_gf_train_multi_on_row_blocks_without_padding_and_without_rows(n):
+    """Four virtual ranks on a path 0 -> 1 -> ... with ascending edges, d = 3, 4 sweeps, bit for bit against gemhip_gf_train: n = 4 (one row per rank,
+    n_pad == n: no padded copy of the table), n = 5 (blocks of 2: the last rank owns [5, 5) after clamping), n = 3 (fewer nodes than ranks)."""
+    src, dst = np.arange(n - 1, dtype=np.int32), np.arange(1, n, dtype=np.int32)
+    X0 = (0.1 * np.random.RandomState(n).randn(n, 3)).astype(np.float32)
+    L = _hip.lib()
+    a = X0.copy(); b = X0.copy()
+    _hip.check(L.gemhip_gf_train(n, len(src), _hip.ptr(src, C.c_int32), _hip.ptr(dst, C.c_int32), None, 3, 0.05, 0.01, 4, _hip.ptr(a, C.c_float), None))
+    st = (C.c_double * 8)()
+    _hip.check(L.gemhip_gf_train_multi(n, len(src), _hip.ptr(src, C.c_int32), _hip.ptr(dst, C.c_int32), None, 3, 0.05, 0.01, 4, 4, _devs(4), _hip.ptr(b, C.c_float), st))
+    assert np.array_equal(a, b) and not np.array_equal(b, X0)
+    assert st[1] == n - 1 and st[4] == 4 and st[5] == 1.0
+
+
 def test_gf_train_multi_refuses_an_order_it_cannot_shard(karate):
     """karate's insertion order 0, 31, 21, ... visits sources out of id order: sharded ranks would read rows 'already updated' in the same sweep.
     One GPU handles it (levels); n_gpus > 1 says so instead of training something else."""
@@ -117,6 +132,26 @@ def test_n2v_train_multi_deterministic_equals_the_oracle_schedule(sbm1024, ranks
     assert st[3] == pairs and st[5] == ranks
     rp, cs, _ = oracle.sorted_csr(n, src, dst, None)
     assert pairs == len(oracle.sgns_pairs(oracle.n2v_walks(rp, cs, None, None, 1.0, 1.0, r, L, seed, flags), win, 0, 0, seed))
+    assert np.abs(X - want).max() <= 2e-4 * np.abs(want).max() + 1e-6
+
+
+@pytest.mark.parametrize('flags', [11, 27])
+def test_n2v_train_multi_with_empty_episode_slices(flags):
+    """A 6-node ring (both directions stored), one walk per node, 4 virtual ranks, 3 episodes: every shard has one or two walks, so some of its episode
+    slices are empty -- their work items are skipped by the kernel's `j >= present` test while alpha still advances by seg_len >= 1 per episode.  Both
+    table layouts against the oracle's restatement of the schedule; every pair of the sequential corpus exactly once (150 of them)."""
+    n, d, L, r, win, seed = 6, 16, 8, 1, 3, 7
+    src = np.concatenate([np.arange(n), (np.arange(n) + 1) % n]).astype(np.int32)
+    dst = np.concatenate([(np.arange(n) + 1) % n, np.arange(n)]).astype(np.int32)
+    row_ptr, col, _ = to_csr(n, src, dst, None)
+    X = np.empty((n, d), np.float32)
+    st = (C.c_double * 8)()
+    _hip.check(_hip.lib().gemhip_n2v_train_multi(n, len(col), _hip.ptr(row_ptr, C.c_int64), _hip.ptr(col, C.c_int32), None, d, L, r, win, 1, 1.0, 1.0, seed,
+                                                 flags | 4, 4, _devs(4), 3, _hip.ptr(X, C.c_float), st))
+    want, pairs = _oracle_multi_schedule(n, src, dst, d, L, r, win, seed, flags, 4, 3)
+    rp, cs, _ = oracle.sorted_csr(n, src, dst, None)
+    assert pairs == 150 == len(oracle.sgns_pairs(oracle.n2v_walks(rp, cs, None, None, 1.0, 1.0, r, L, seed, flags), win, 0, 0, seed))
+    assert st[3] == pairs and st[5] == 4 and st[2] == n * L
     assert np.abs(X - want).max() <= 2e-4 * np.abs(want).max() + 1e-6
 
 
