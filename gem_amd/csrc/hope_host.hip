@@ -5,6 +5,7 @@
 #include "sym_eig.hpp"
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 
@@ -301,6 +302,26 @@ void fill_solve_stats(double *stats, double ms, double spmm_count, double spmm_c
 }
 
 // ------------------------------------------------------------------ set-up
+HopeKnobs hope_knobs_from_env(const char *(*lookup)(const char *))
+{
+    HopeKnobs kn;
+    if (const char *e = lookup("GEMHIP_HOPE_SPMM16")) kn.spmm16 = atoi(e);
+    if (const char *e = lookup("GEMHIP_HOPE_SPMM16_U")) kn.spmm16_u = atoi(e);
+    if (const char *e = lookup("GEMHIP_HOPE_COLMAX2")) kn.colmax2 = atoi(e);
+    if (const char *e = lookup("GEMHIP_HOPE_SYM")) kn.sym = atoi(e) != 0;
+    if (const char *e = lookup("GEMHIP_HOPE_SYM_AMP")) kn.sym_amp = std::max(10.0, atof(e));
+    if (const char *e = lookup("GEMHIP_HOPE_SYM_AMP0")) kn.sym_amp0 = std::max(10.0, atof(e));
+    if (const char *e = lookup("GEMHIP_HOPE_SYM_MAXDEG")) kn.sym_maxdeg = std::max(2, atoi(e));
+    if (const char *e = lookup("GEMHIP_HOPE_SYM_FUSED_RR")) kn.sym_fused_rr = atoi(e) != 0;
+    kn.no_lock = lookup("GEMHIP_HOPE_NO_LOCK") != nullptr;
+    kn.fixed_depth = lookup("GEMHIP_HOPE_FIXED_DEPTH") != nullptr;
+    kn.host_project = lookup("GEMHIP_HOPE_HOST_PROJECT") != nullptr;
+    kn.debug = lookup("GEMHIP_HOPE_DEBUG") != nullptr;
+    if (const char *e = lookup("GEMHIP_HOPE_BASIS_COLS")) { kn.has_basis_cols = true; kn.basis_cols = atoi(e); }
+    if (const char *e = lookup("GEMHIP_HOPE_DEPTH_COLS")) { kn.has_depth_cols = true; kn.depth_cols = atoi(e); }
+    return kn;
+}
+
 CsrError check_csr_arrays(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, int64_t *bad_edge)
 {
     if (!(n >= 2 && nnz >= 0 && row_ptr && (nnz == 0 || col))) return CsrError::BAD_ARGUMENTS;

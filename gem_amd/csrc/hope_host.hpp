@@ -1,6 +1,6 @@
 // hope_host.hpp -- the host arithmetic of HOPE / Laplacian Eigenmaps / LLE (hope_host.hip): the fp64 small-matrix steps between the launches, the
 // scheduling rules of the two solvers, the choice of the k outputs, the CSR set-up.  Plain C++, no HIP: everything here runs on a CPU
-// (scripts/build_asan_hope_host.sh, tests/test_hope_host.py); hope.hip launches, asks these functions what to do next, and words the refusals.
+// (scripts/build_asan_hope_host.sh, tests/test_hope_host.py); the solvers (hope_solve.hip) launch and ask these functions what to do next; the entry points (hope.hip) word the refusals.
 // Small matrices are row-major fp64 std::vectors unless a comment says otherwise.
 #pragma once
 #include <cstdint>
@@ -70,6 +70,31 @@ void select_outputs(std::vector<OutCand> &cand, int k, int nl, int ma, const std
 bool flip_negative_columns(int mc, int k, const std::vector<double> &colmax, std::vector<double> &Cu, std::vector<double> &Cv);
 void fill_solve_stats(double *stats, double ms, double spmm_count, double spmm_cols, double terms, double basis, double cycles, double change, double br,
                       double residual, double spmm_ms);
+
+// ---------------------------------------------------------------- knobs
+// The fourteen GEMHIP_HOPE_* variables, read in one place.  Hope (hope_ops.hpp) holds one of these; it is filled when the state is made and again at
+// the start of a plan set-up, a solve and an SVD-error estimate, so a variable set between two calls of a process is seen by the second.
+struct HopeKnobs {
+    int spmm16 = 1;                // _SPMM16: 0 = one row per wavefront, else 16 lanes per row up to 128 columns
+    int spmm16_u = 0;              // _SPMM16_U: gathers in flight per row and round (>= 8, >= 4, else 2); <= 0 = by the block's width
+    int colmax2 = 1;               // _COLMAX2: 0 = one block per column, else two coalesced passes
+    int sym = -1;                  // _SYM: -1 = unset (the size rule of solve_operator decides), 0 = never the eigen-path, 1 = at any size
+    double sym_amp = 1e4;          // _SYM_AMP, _SYM_AMP0: filter growth per cycle / of the first cycle, at least 10
+    double sym_amp0 = 1e3;
+    int sym_maxdeg = 32;           // _SYM_MAXDEG: filter degree per cycle, at least 2 (measured at SBM 100k/1M: 30-32 is cheapest, scripts/ab_hope_sym.py)
+    bool sym_fused_rr = true;      // _SYM_FUSED_RR: off for a value that reads as 0
+    bool no_lock = false;          // _NO_LOCK, _FIXED_DEPTH, _HOST_PROJECT, _DEBUG: on by presence, whatever the value
+    bool fixed_depth = false;
+    bool host_project = false;
+    bool debug = false;
+    bool has_basis_cols = false;   // _BASIS_COLS, _DEPTH_COLS: optional; the value goes to krylov_basis_capacity / krylov_steps_after_lock as it is
+    bool has_depth_cols = false;
+    int basis_cols = 0, depth_cols = 0;
+    const int *basis_cols_override() const { return has_basis_cols ? &basis_cols : nullptr; }
+    const int *depth_cols_override() const { return has_depth_cols ? &depth_cols : nullptr; }
+};
+// lookup(name): the variable's value or null -- getenv in the library, a table in the CPU tests
+HopeKnobs hope_knobs_from_env(const char *(*lookup)(const char *));
 
 // ---------------------------------------------------------------- set-up
 enum class CsrError { NONE = 0, BAD_ARGUMENTS, ROW_PTR, COLUMN };

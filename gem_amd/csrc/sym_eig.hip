@@ -1,4 +1,4 @@
-// sym_eig.hip -- the host symmetric eigensolver (fp64) behind the HOPE / Laplacian Eigenmaps / LLE solvers of hope.hip; interface: sym_eig.hpp.
+// sym_eig.hip -- the host symmetric eigensolver (fp64) behind the HOPE / Laplacian Eigenmaps / LLE solvers of hope_solve.hip; interface: sym_eig.hpp.
 // Householder tridiagonalisation + implicit-shift QL (the classical EISPACK tred2/tql2 pair) for the projected eigenproblems (<= 512 x 512), a
 // partial solver for the top m pairs, and the host threads of their O(n^3) phases.
 // HIP-FREE BY RULE: no HIP header, nothing from common.hpp, no kernel -- the file compiles with plain `clang++ -x c++ -std=c++17` as well as with

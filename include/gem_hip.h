@@ -488,7 +488,7 @@ int gemhip_hope_tsgemm(int64_t n, int32_t m, int32_t b2, const float *X_host, co
 /* -------------------------------------------------- test hooks (HOPE building blocks under the solvers' calling conventions)
  * Like gemhip_test_wave_sum6: not part of the product API.  Each hook uploads its host blocks, calls the host function the
  * solvers call (spmm, gram, gram2, tsgemm, ritz_rotate, colmax, project_out, apply_sym_op, lincomb, randn in
- * gem_amd/csrc/hope.hip) on a state of its own, and copies the result back; blocking.  Unlike the three exports above,
+ * gem_amd/csrc/hope_ops.hip; the hooks themselves: hope_hooks.hip) on a state of its own, and copies the result back; blocking.  Unlike the three exports above,
  * every dense block has its own leading dimension (ld >= logical columns; an "off" argument is a column offset into the
  * block, as in `Vall + nl`), and blocks named *_inout are uploaded WHOLE before the call and downloaded WHOLE after it:
  * a caller that fills the padding columns with a sentinel sees every write outside the logical columns.
@@ -498,7 +498,7 @@ int gemhip_hope_tsgemm(int64_t n, int32_t m, int32_t b2, const float *X_host, co
  *                the very device block of X (the (I + M) X and X - P X calls); w2_is_y: W2 is the very device block of Y,
  *                holding Y_inout's contents (apply_sym_op kind 2).  launched_out (may be NULL) receives the instantiation the
  *                dispatch chose: {CPL16, U} of hope_spmm16_kernel or {CPL, 0} of hope_spmm_kernel.  Without an override the environment variables
- *                GEMHIP_HOPE_SPMM16 / GEMHIP_HOPE_SPMM16_U / GEMHIP_HOPE_COLMAX2 decide, as in the solvers.
+ *                GEMHIP_HOPE_SPMM16 / GEMHIP_HOPE_SPMM16_U / GEMHIP_HOPE_COLMAX2 decide, as in the solvers (read at every hook call).
  *   gram       : G[m1][m2] = X[:, xoff:+m1]^T Y[:, yoff:+m2] (fp64); Y_host NULL = Y is X's device block; Gf_host (optional):
  *                the same values rounded to fp32 on the device (what project_out feeds its GEMM).
  *   gram2      : two such products in one call (shared scratch, one round trip).

@@ -4,9 +4,12 @@
 //   hope_host_driver <group> <in> <out>      group: dense | ritz | sym | krylov | out | csr
 //       Both files are a sequence of fp64 arrays, each preceded by its length as one fp64 (integers travel as fp64 too).  The arrays of every
 //       group are listed at its function below; tests/test_hope_host.py writes the inputs and compares the outputs with numpy.
+//   hope_host_driver knobs <out> [NAME=VALUE ...]
+//       hope_knobs_from_env over exactly the variables given (a table, never the process's environment): one array, listed at run_knobs below.
 //   hope_host_driver self
 //       every function on inputs generated from seeds, the awkward ones included (a null Gram column, a repeated column, keep = 2, no column to
-//       lock, want = 1, tau = 0, tau >= 1, every kind, an empty row, nnz = 0, one differing weight, duplicate entries); checks C^T G C = I and the
+//       lock, want = 1, tau = 0, tau >= 1, every kind, an empty row, nnz = 0, one differing weight, duplicate entries), the knobs (defaults, each
+//       variable alone, the clamps, present-but-empty) and check_csr_arrays against the test hooks' rule; checks C^T G C = I and the
 //       like, prints one line per check, returns 1 if one failed.  scripts/build_asan_hope_host.sh runs this form under AddressSanitizer and UBSan.
 #include "../../gem_amd/csrc/hope_host.hpp"
 #include "../../gem_amd/csrc/sym_eig.hpp"
@@ -163,6 +166,28 @@ std::vector<Vec> run_csr(const std::vector<Vec> &in)
     return out;
 }
 
+// The environment hope_knobs_from_env is shown: NAME=VALUE strings, never the process's own
+std::vector<std::string> fake_env;
+const char *fake_lookup(const char *name)
+{
+    const size_t len = strlen(name);
+    for (const std::string &s : fake_env)
+        if (s.size() > len && s.compare(0, len, name) == 0 && s[len] == '=') return s.c_str() + len + 1;
+    return nullptr;
+}
+
+// out: {spmm16, spmm16_u, colmax2, sym, sym_amp, sym_amp0, sym_maxdeg, sym_fused_rr, no_lock, fixed_depth, host_project, debug, has_basis_cols, basis_cols,
+// has_depth_cols, depth_cols} of hope_knobs_from_env over exactly the variables in `env`; the two overrides are read through their accessors
+Vec run_knobs(const std::vector<std::string> &env)
+{
+    fake_env = env;
+    const HopeKnobs kn = hope_knobs_from_env(fake_lookup);
+    const int *bc = kn.basis_cols_override(), *dc = kn.depth_cols_override();
+    return {(double)kn.spmm16, (double)kn.spmm16_u, (double)kn.colmax2, (double)kn.sym, kn.sym_amp, kn.sym_amp0, (double)kn.sym_maxdeg, (double)kn.sym_fused_rr,
+            (double)kn.no_lock, (double)kn.fixed_depth, (double)kn.host_project, (double)kn.debug, (double)(bc != nullptr), bc ? (double)*bc : 0.0,
+            (double)(dc != nullptr), dc ? (double)*dc : 0.0};
+}
+
 // ------------------------------------------------------------------ self
 int failures = 0;
 void check(const char *what, bool ok) { printf("%-72s %s\n", what, ok ? "ok" : "FAILED"); failures += !ok; }
@@ -307,6 +332,51 @@ void self_csr()
     o = run_csr({{1, 0, 0, 0.5, 3}, {0, 0}, Vec(), Vec()});
     check("csr: n < 2 is refused", o[0][0] == (double)(int)CsrError::BAD_ARGUMENTS);
     check("katz_terms: 1 at br <= 0, capped at 400", katz_terms(0.0) == 1 && katz_terms(-1.0) == 1 && katz_terms(0.9499) == 359 && katz_terms(0.99) == 400);
+    // check_csr_arrays against the rule of the test hooks (hook_csr_ok, hope_hooks.hip: n >= 1, both ends of row_ptr, row_ptr never decreasing, every
+    // column in range).  The two agree on five of these inputs and differ on two, which is why the hooks keep their own.
+    const int64_t rp3[] = {0, 2, 3, 3}, rp_first[] = {1, 2, 3, 3}, rp_down[] = {0, 3, 2, 3}, rp_zero[] = {0, 0, 0, 0}, rp_one[] = {0, 0};
+    const int32_t ci3[] = {1, 2, 0}, ci_neg[] = {1, -1, 0}, ci_n[] = {1, 3, 0};
+    int64_t bad = -1;
+    check("validators: n = 0 is refused (as by the hooks)", check_csr_arrays(0, 0, rp_one, nullptr, &bad) == CsrError::BAD_ARGUMENTS);
+    check("validators: nnz = 0 with col == NULL is accepted (as by the hooks)", check_csr_arrays(3, 0, rp_zero, nullptr, &bad) == CsrError::NONE);
+    check("validators: row_ptr[0] != 0 is refused (as by the hooks)", check_csr_arrays(3, 3, rp_first, ci3, &bad) == CsrError::ROW_PTR);
+    check("validators: row_ptr[n] != nnz is refused (as by the hooks)", check_csr_arrays(3, 2, rp3, ci3, &bad) == CsrError::ROW_PTR);
+    check("validators: col = -1 is refused at its position (as by the hooks)", check_csr_arrays(3, 3, rp3, ci_neg, &bad) == CsrError::COLUMN && bad == 1);
+    check("validators: col = n is refused at its position (as by the hooks)", check_csr_arrays(3, 3, rp3, ci_n, &bad) == CsrError::COLUMN && bad == 1);
+    check("validators DIFFER: a decreasing row_ptr with consistent ends passes check_csr_arrays (the hooks refuse it)", check_csr_arrays(3, 3, rp_down, ci3, &bad) == CsrError::NONE);
+    check("validators DIFFER: n = 1 is refused by check_csr_arrays (the hooks take it)", check_csr_arrays(1, 0, rp_one, nullptr, &bad) == CsrError::BAD_ARGUMENTS);
+}
+
+void self_knobs()
+{
+    const Vec defaults = {1, 0, 1, -1, 1e4, 1e3, 32, 1, 0, 0, 0, 0, 0, 0, 0, 0};
+    check("knobs: nothing set gives the defaults", run_knobs({}) == defaults);
+    check("knobs: other variables are not looked at", run_knobs({"GEMHIP_HOPE_SPMM16_UX=4", "GEMHIP_SGNS_FRESH=3", "HOPE_SYM=1"}) == defaults);
+    // each variable alone: {assignment, index of the value it changes, the value}; everything else stays at its default
+    const struct { const char *env; int at; double v; } one[] = {
+        {"GEMHIP_HOPE_SPMM16=0", 0, 0}, {"GEMHIP_HOPE_SPMM16_U=2", 1, 2}, {"GEMHIP_HOPE_COLMAX2=0", 2, 0}, {"GEMHIP_HOPE_SYM=0", 3, 0}, {"GEMHIP_HOPE_SYM=1", 3, 1},
+        {"GEMHIP_HOPE_SYM=7", 3, 1}, {"GEMHIP_HOPE_SYM=", 3, 0}, {"GEMHIP_HOPE_SYM_AMP=250.5", 4, 250.5}, {"GEMHIP_HOPE_SYM_AMP=3", 4, 10}, {"GEMHIP_HOPE_SYM_AMP0=30", 5, 30},
+        {"GEMHIP_HOPE_SYM_AMP0=-1", 5, 10}, {"GEMHIP_HOPE_SYM_MAXDEG=12", 6, 12}, {"GEMHIP_HOPE_SYM_MAXDEG=1", 6, 2}, {"GEMHIP_HOPE_SYM_FUSED_RR=0", 7, 0},
+        {"GEMHIP_HOPE_SYM_FUSED_RR=1", 7, 1}, {"GEMHIP_HOPE_NO_LOCK=1", 8, 1}, {"GEMHIP_HOPE_NO_LOCK=", 8, 1}, {"GEMHIP_HOPE_NO_LOCK=0", 8, 1},
+        {"GEMHIP_HOPE_FIXED_DEPTH=1", 9, 1}, {"GEMHIP_HOPE_FIXED_DEPTH=", 9, 1}, {"GEMHIP_HOPE_HOST_PROJECT=1", 10, 1}, {"GEMHIP_HOPE_HOST_PROJECT=", 10, 1},
+        {"GEMHIP_HOPE_DEBUG=1", 11, 1}, {"GEMHIP_HOPE_DEBUG=", 11, 1}};
+    for (const auto &c : one) {
+        Vec want = defaults;
+        want[c.at] = c.v;
+        check((std::string("knobs: ") + c.env).c_str(), run_knobs({c.env}) == want);
+    }
+    Vec want = defaults;
+    want[12] = 1; want[13] = 700;
+    check("knobs: GEMHIP_HOPE_BASIS_COLS=700 is passed on", run_knobs({"GEMHIP_HOPE_BASIS_COLS=700"}) == want);
+    want[13] = -5;
+    check("knobs: GEMHIP_HOPE_BASIS_COLS=-5 is passed on as it is (krylov_basis_capacity clamps)", run_knobs({"GEMHIP_HOPE_BASIS_COLS=-5"}) == want);
+    want = defaults;
+    want[14] = 1; want[15] = 64;
+    check("knobs: GEMHIP_HOPE_DEPTH_COLS=64 is passed on", run_knobs({"GEMHIP_HOPE_DEPTH_COLS=64"}) == want);
+    check("knobs: all at once", run_knobs({"GEMHIP_HOPE_SPMM16=0", "GEMHIP_HOPE_SPMM16_U=4", "GEMHIP_HOPE_COLMAX2=0", "GEMHIP_HOPE_SYM=1", "GEMHIP_HOPE_SYM_AMP=100",
+                                          "GEMHIP_HOPE_SYM_AMP0=50", "GEMHIP_HOPE_SYM_MAXDEG=8", "GEMHIP_HOPE_SYM_FUSED_RR=0", "GEMHIP_HOPE_NO_LOCK=1",
+                                          "GEMHIP_HOPE_FIXED_DEPTH=1", "GEMHIP_HOPE_HOST_PROJECT=1", "GEMHIP_HOPE_DEBUG=1", "GEMHIP_HOPE_BASIS_COLS=96",
+                                          "GEMHIP_HOPE_DEPTH_COLS=48"}) == Vec({0, 4, 0, 1, 100, 50, 8, 0, 1, 1, 1, 1, 1, 96, 1, 48}));
 }
 
 }  // namespace
@@ -315,10 +385,11 @@ int main(int argc, char **argv)
 {
     if (argc == 2 && !strcmp(argv[1], "self")) {
         for (uint32_t seed : {1u, 2u, 3u}) self_dense(seed);
-        self_rules(); self_outputs(); self_csr();
+        self_rules(); self_outputs(); self_csr(); self_knobs();
         printf("%d checks failed\n", failures);
         return failures ? 1 : 0;
     }
+    if (argc >= 3 && !strcmp(argv[1], "knobs")) return write_arrays(argv[2], {run_knobs(std::vector<std::string>(argv + 3, argv + argc))}) ? 0 : 2;
     if (argc == 4) {
         std::vector<Vec> in, out;
         if (!read_arrays(argv[2], in)) { fprintf(stderr, "hope_host_driver: bad input %s\n", argv[2]); return 2; }
@@ -328,6 +399,6 @@ int main(int argc, char **argv)
         out = g == "dense" ? run_dense(in) : g == "ritz" ? run_ritz(in) : g == "sym" ? run_sym(in) : g == "krylov" ? run_krylov(in) : g == "out" ? run_out(in) : run_csr(in);
         return write_arrays(argv[3], out) ? 0 : 2;
     }
-    fprintf(stderr, "usage: %s self | dense|ritz|sym|krylov|out|csr <in> <out>\n", argv[0]);
+    fprintf(stderr, "usage: %s self | dense|ritz|sym|krylov|out|csr <in> <out> | knobs <out> [NAME=VALUE ...]\n", argv[0]);
     return 2;
 }

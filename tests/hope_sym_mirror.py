@@ -1,4 +1,4 @@
-"""numpy mirror of the symmetric eigen-path of gem_amd/csrc/hope.hip (sym_filter_svd): same steps, same constants, fp32 blocks and
+"""numpy mirror of the symmetric eigen-path of gem_amd/csrc/hope_solve.hip (sym_filter_svd): same steps, same constants, fp32 blocks and
 fp64 small matrices.  Test infrastructure only (the product path is the HIP kernel): it was used to design the solver on the CPU and it
 pins the algorithm's logic -- two-sided selection by |f(lambda)|, cut-off from the middle of the oversampling columns, degree caps,
 locking, in-filter deflation -- against scipy in tests/test_hope_sym_mirror_cpu.py.

@@ -77,7 +77,7 @@ def graph(n):
 
 
 def expected_instantiation(b, variant):
-    """hope.hip spmm(): the 16-lane kernel up to 128 columns -- <ceil(b / 16), U> with U = 8 up to 48 columns and 4 beyond, 6 sixteenths only with
+    """hope_ops.hip spmm(): the 16-lane kernel up to 128 columns -- <ceil(b / 16), U> with U = 8 up to 48 columns and 4 beyond, 6 sixteenths only with
     U <= 4, 7 and 8 sixteenths as <8, 2> -- else one row per wavefront, <CPL> in {1, 2, 4, 8} (reported with U = 0)."""
     if variant == 1 or b > 128:
         cpl = (b + 63) // 64
@@ -148,7 +148,7 @@ SPMM16_WIDTHS = [1, 16, 17, 33, 48, 49, 64, 65, 81, 96, 97, 113, 128]
 
 
 def u_variants(b):
-    """Forced U values that have an instantiation of their own at this width (hope.hip spmm(): U = 8 up to 80 columns, U = 4 up to 96)."""
+    """Forced U values that have an instantiation of their own at this width (hope_ops.hip spmm(): U = 8 up to 80 columns, U = 4 up to 96)."""
     c16 = (b + 15) // 16
     return [2, 4, 8] if c16 <= 5 else [2, 4] if c16 <= 6 else [2]
 
@@ -178,6 +178,46 @@ def test_spmm_variants_are_bit_identical(b):
             assert np.array_equal(outs[v].view(np.uint32), outs[0].view(np.uint32)), 'U = %d differs from the default dispatch at b = %d' % (v, b)
         _, bound = spmm_ref(g, alpha, X, 1.0, Wadd)
         assert np.all(np.abs(outs[1].astype(np.float64) - outs[0].astype(np.float64)) <= 2 * bound)
+
+
+def test_spmm_knobs_are_read_at_every_call(monkeypatch):
+    """GEMHIP_HOPE_SPMM16 and GEMHIP_HOPE_SPMM16_U are read when a hook (a plan set-up, a solve) starts, not frozen at the first SpMM of the
+    process: three production-dispatch calls (variant 0) in one process, under SPMM16=0, under SPMM16=1 with SPMM16_U=2, and with both unset,
+    launch <1> of the one-row kernel, <1, 2> and <1, 8> of the 16-lane kernel at b = 8.
+
+    The two 16-lane outputs are equal bit for bit, padding sentinel included.  The one-row kernel's is not held to that: both kernels add a row's
+    neighbours in CSR order, but the one-row kernel's multiply-adds are fused and the 16-lane kernel's are not (hope_ops.hip says so at the
+    kernel, test_spmm_variants_are_bit_identical above holds them to rounding only), so the outputs are not bit-equal before this change
+    either.  All three are therefore compared with the fp64 reference under that test's derived bound, elementwise, and their padding must
+    hold the sentinel."""
+    n, b, ld = 200, 8, 11
+    g = make_graph(n, 207)
+    rng = np.random.RandomState(8)
+    X = rng.randn(n, b).astype(np.float32)
+    alpha = f32(0.37)
+    ref, bound = spmm_ref(g, alpha, X)
+
+    def call(env):
+        for name in ('GEMHIP_HOPE_SPMM16', 'GEMHIP_HOPE_SPMM16_U'):
+            monkeypatch.delenv(name, raising=False)
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
+        Y, launched = np.full((n, ld), SENT, np.float32), np.zeros(2, np.int32)
+        _hip.check(_hip.lib().gemhip_test_hope_spmm(n, len(g['ci']), _hip.ptr(g['rp'], C.c_int64), _hip.ptr(g['ci'], C.c_int32), fp(g['va']), 0, alpha, b,
+                                                    fp(padded(X, ld)), ld, 1.0, None, 0, 0.0, None, 0, 0, 0, fp(Y), ld, _hip.ptr(launched, C.c_int32)))
+        return Y, tuple(launched)
+
+    one_row, l0 = call({'GEMHIP_HOPE_SPMM16': '0'})
+    u2, l1 = call({'GEMHIP_HOPE_SPMM16': '1', 'GEMHIP_HOPE_SPMM16_U': '2'})
+    auto, l2 = call({})
+    assert (l0, l1, l2) == ((1, 0), (1, 2), (1, 8))
+    assert np.array_equal(u2.view(np.uint32), auto.view(np.uint32)), 'U = 2 and the default U differ'
+    for name, Y in (('SPMM16=0', one_row), ('SPMM16_U=2', u2), ('unset', auto)):
+        err = np.abs(Y[:, :b].astype(np.float64) - ref)
+        print('%s: max error / bound = %.3g' % (name, (err / np.maximum(bound, 1e-300)).max()))
+        assert np.all(err <= bound), name
+        assert_padding(Y, 0, b)
+    print('one-row against 16-lane: %d of %d values differ in their bits' % (np.count_nonzero(one_row.view(np.uint32) != auto.view(np.uint32)), one_row.size))
 
 
 # ------------------------------------------------------------------------------------------------------------------ Ritz rotation

@@ -151,7 +151,7 @@ def test_all_64_singular_values_of_the_directed_graph_vs_arpack():
 
 
 def test_symmetric_eigen_path_agrees_with_the_block_krylov_path(monkeypatch):
-    """Undirected graphs take the Chebyshev-filtered eigen-path on A (hope.hip sym_filter_svd; automatic from 16384 nodes, forced here
+    """Undirected graphs take the Chebyshev-filtered eigen-path on A (hope_solve.hip sym_filter_svd; automatic from 16384 nodes, forced here
     at 8192): same singular values and the same rank-k reconstruction U S V^T as the general block-Krylov solver on S^T S, which the
     other tests pin against the reference's runs; a directed graph never takes it."""
     g = sbm_graph(8192, 81920, 8, seed=11)

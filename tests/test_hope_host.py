@@ -56,6 +56,34 @@ def test_self_checks_pass(driver):
     assert run.returncode == 0, run.stdout.decode()[-3000:] + run.stderr.decode()[-2000:]
 
 
+KNOB_DEFAULTS = dict(spmm16=1, spmm16_u=0, colmax2=1, sym=-1, sym_amp=1e4, sym_amp0=1e3, sym_maxdeg=32, sym_fused_rr=1, no_lock=0, fixed_depth=0,
+                     host_project=0, debug=0, has_basis_cols=0, basis_cols=0, has_depth_cols=0, depth_cols=0)
+
+
+@pytest.mark.parametrize('env,changed', [
+    ({}, {}),                                                                                   # nothing set: the defaults
+    ({'SPMM16': '0'}, dict(spmm16=0)), ({'SPMM16_U': '2'}, dict(spmm16_u=2)), ({'COLMAX2': '0'}, dict(colmax2=0)),     # each variable alone
+    ({'SYM': '0'}, dict(sym=0)), ({'SYM': '1'}, dict(sym=1)), ({'SYM': '5'}, dict(sym=1)),     # tri-state: unset (-1), 0, non-zero
+    ({'SYM_AMP': '250.5'}, dict(sym_amp=250.5)), ({'SYM_AMP': '3'}, dict(sym_amp=10.0)),       # ... and the clamps
+    ({'SYM_AMP0': '30'}, dict(sym_amp0=30.0)), ({'SYM_AMP0': '3'}, dict(sym_amp0=10.0)),
+    ({'SYM_MAXDEG': '12'}, dict(sym_maxdeg=12)), ({'SYM_MAXDEG': '1'}, dict(sym_maxdeg=2)),
+    ({'SYM_FUSED_RR': '0'}, dict(sym_fused_rr=0)), ({'SYM_FUSED_RR': '1'}, {}),
+    ({'NO_LOCK': '1'}, dict(no_lock=1)), ({'FIXED_DEPTH': '1'}, dict(fixed_depth=1)), ({'HOST_PROJECT': '1'}, dict(host_project=1)), ({'DEBUG': '1'}, dict(debug=1)),
+    ({'NO_LOCK': ''}, dict(no_lock=1)), ({'FIXED_DEPTH': ''}, dict(fixed_depth=1)), ({'HOST_PROJECT': ''}, dict(host_project=1)), ({'DEBUG': ''}, dict(debug=1)),
+    ({'NO_LOCK': '0'}, dict(no_lock=1)),                                                        # on by presence, whatever the value
+    ({'BASIS_COLS': '700'}, dict(has_basis_cols=1, basis_cols=700)), ({'DEPTH_COLS': '64'}, dict(has_depth_cols=1, depth_cols=64)),
+    ({'SPMM16': '0', 'SPMM16_U': '4', 'SYM': '1', 'SYM_AMP': '100', 'DEBUG': '', 'DEPTH_COLS': '48'},
+     dict(spmm16=0, spmm16_u=4, sym=1, sym_amp=100.0, debug=1, has_depth_cols=1, depth_cols=48)),
+])
+def test_knobs_from_a_table(driver, tmp_path, env, changed):
+    """hope_knobs_from_env over a lookup table (never the process environment): the fourteen GEMHIP_HOPE_* variables, their defaults and clamps"""
+    out = str(tmp_path / 'knobs')
+    subprocess.check_call([driver.exe, 'knobs', out] + ['GEMHIP_HOPE_%s=%s' % kv for kv in env.items()], env={'GEMHIP_HOPE_SPMM16': '0', 'GEMHIP_HOPE_DEBUG': '1'})
+    raw = np.fromfile(out, np.float64)
+    assert raw[0] == len(KNOB_DEFAULTS) == raw.size - 1
+    assert dict(zip(KNOB_DEFAULTS, raw[1:])) == dict(KNOB_DEFAULTS, **changed)
+
+
 def chol_coef(G):
     return np.linalg.inv(np.linalg.cholesky(G).T)
 

@@ -1,4 +1,4 @@
-"""CPU: the numpy mirror of hope.hip's symmetric eigen-path (tests/hope_sym_mirror.py) against scipy -- the algorithm's logic, without
+"""CPU: the numpy mirror of hope_solve.hip's symmetric eigen-path (tests/hope_sym_mirror.py) against scipy -- the algorithm's logic, without
 a GPU: selection of the k largest |f(lambda)| from BOTH ends of the spectrum, u = sign(f(lambda)) q, convergence within the cycle budget,
 and the SpMM-column count that motivates the path (the block-Krylov solver on S^T S applies 18 SpMMs per Krylov step)."""
 import numpy as np

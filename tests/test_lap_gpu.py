@@ -67,7 +67,7 @@ def test_lle_karate_and_sbm(karate, sbm1024):
 
 
 def test_eigen_path_agrees_with_block_krylov_and_scipy(monkeypatch):
-    """From 16384 nodes up Laplacian Eigenmaps runs HOPE's Chebyshev-filtered eigen-path on D^-1/2 A D^-1/2 (hope.hip sym_filter_svd,
+    """From 16384 nodes up Laplacian Eigenmaps runs HOPE's Chebyshev-filtered eigen-path on D^-1/2 A D^-1/2 (hope_solve.hip sym_filter_svd,
     kind 1).  SBM 20000/200000, d=16: eigenvalues of L_sym against scipy eigsh and against the block-Krylov path, community vectors one by
     one, the subspace by its projector."""
     import scipy.sparse as sp
@@ -103,7 +103,7 @@ def test_eigen_path_agrees_with_block_krylov_and_scipy(monkeypatch):
 
 
 def test_lle_eigen_path_at_20k(monkeypatch):
-    """From 16384 nodes up LLE runs the Chebyshev-filtered eigen-path on N^T N, N = I - D^-1 A (hope.hip sym_filter_svd kind 2: the
+    """From 16384 nodes up LLE runs the Chebyshev-filtered eigen-path on N^T N, N = I - D^-1 A (hope_solve.hip sym_filter_svd kind 2: the
     SMALLEST eigenvalues, two SpMMs per application).  SBM 20000/200000, d=16: every returned pair satisfies ||N v|| = s and
     N^T N v = s^2 v, V is orthonormal, the constant vector comes first (s = 0), the 7 community singular values equal the ones the numpy
     mirror of the solver converged to on the CPU (which agrees with scipy svds(which='SM') at 2000 nodes to 2e-6), and the block-Krylov
