@@ -98,6 +98,13 @@ _SIGS = {
     'gemhip_test_hope_lincomb': (C.c_int, [C.c_int64, C.c_int32, C.c_float, f32p, C.c_int32, C.c_float, f32p, C.c_int32, C.c_float, f32p, C.c_int32, C.c_int32,
                                            f32p, C.c_int32]),
     'gemhip_test_hope_randn': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_uint64, f32p]),
+    # ... and what the solvers compose of them: apply_S / apply_ST, cheb_filter, orth / orth_scaled, the set-ups' spectrum estimates
+    'gemhip_test_hope_apply_s': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int32,
+                                           C.c_int32, f32p, C.c_int32]),
+    'gemhip_test_hope_cheb_filter': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_double, C.c_double, f32p, C.c_int32,
+                                               C.c_int32, C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32]),
+    'gemhip_test_hope_orth': (C.c_int, [C.c_int64, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, i32p]),
+    'gemhip_test_hope_spectrum_estimate': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, f64p]),
     'gemhip_eval_sampled_ap': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, f32p, i64p, i32p, C.c_int32, C.c_int64, i32p, f64p]),
     'gemhip_eval_create': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, f32p, C.c_int32, i64p, i32p, C.POINTER(C.c_void_p)]),
     'gemhip_eval_ap': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, i32p, f64p]),

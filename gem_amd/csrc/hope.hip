@@ -27,6 +27,31 @@ struct gemhip_hope_plan {
     double frob2_A = 0.0;                            // sum of the squared edge weights: ||beta A||_F^2 = beta^2 x this (gemhip_hope_plan_svd_error)
 };
 
+// ------------------------------------------------------------------ the two spectrum estimates of the set-ups
+namespace gemhip {
+
+// sigma_max(A) >= rho(A) by power iteration on A^T A (at most 40 steps; the 10 % margin covers what the stopping rule leaves); the max absolute
+// row / column sums bound it too.  H holds A and A^T; row_ptr, col, va: the same A on the host.  Errors are in H.err.
+double katz_rho_estimate(Hope &H, const int64_t *row_ptr, const int32_t *col, const float *va)
+{
+    const double rho = std::sqrt(power_iteration(H, 0.37, 12.9898, 40, 4, 1e-3, true, [&](float *X2, float *y) {
+        spmm(H, false, 1.0f, X2, 2, nullptr, 0, y, 1, 1);                            // y = A x
+        spmm(H, true, 1.0f, y, 1, nullptr, 0, X2 + 1, 2, 1);                         // z = A^T y
+    }));
+    return std::min(std::max(rho * 1.1, 1e-30), abs_sum_bound(H.n, row_ptr, col, va));
+}
+
+// c >= sigma_max(I - P)^2 by power iteration on N^T N (at most 60 steps), with a 5 % margin.  H holds P and P^T.  Errors are in H.err.
+double lle_shift_estimate(Hope &H)
+{
+    const double est = power_iteration(H, 0.61, 7.31, 60, 8, 1e-4, false, [&](float *X2, float *t) {
+        apply_sym_op(H, 2, 1.0f, X2, 2, 1, t, 1, X2 + 1, 2, 1.0f, nullptr, 0, 0.f, nullptr, 0);            // z = N^T N x
+    });
+    return est > 0.0 ? est * 1.05 : 4.0;
+}
+
+}  // namespace gemhip
+
 // Graph-dependent setup of the Katz operator: A and A^T in CSR on the device, number of series terms from sigma_max(A).
 static int hope_setup(gemhip_hope_plan &P, int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, float beta)
 {
@@ -39,13 +64,8 @@ static int hope_setup(gemhip_hope_plan &P, int64_t n, int64_t nnz, const int64_t
     const CsrT T = transpose_csr(n, nnz, row_ptr, col, va.data());
     P.symmetric = csr_is_symmetric(n, nnz, row_ptr, T);
     if (upload_csr(H, "hope", n, nnz, row_ptr, col, va.data(), &T)) return H.err;
-    // sigma_max(A) >= rho(A) by power iteration on A^T A (at most 40 steps; the 10 % margin covers what the stopping rule leaves)
-    double rho = std::sqrt(power_iteration(H, 0.37, 12.9898, 40, 4, 1e-3, true, [&](float *X2, float *y) {
-        spmm(H, false, 1.0f, X2, 2, nullptr, 0, y, 1, 1);                            // y = A x
-        spmm(H, true, 1.0f, y, 1, nullptr, 0, X2 + 1, 2, 1);                         // z = A^T y
-    }));
+    const double rho = katz_rho_estimate(H, row_ptr, col, va.data());
     if (H.err) return H.err;
-    rho = std::min(std::max(rho * 1.1, 1e-30), abs_sum_bound(n, row_ptr, col, va.data()));     // the max absolute row / column sums bound it too
     const double br = std::fabs((double)beta) * rho;
     if (!(br < 0.95))
         return fail(GEMHIP_E_NOTCONVERGED, "hope: beta*rho(A) ~ %.3f >= 0.95: the Katz series (I - beta A)^-1 = sum (beta A)^t does not converge fast "
@@ -294,12 +314,8 @@ extern "C" int gemhip_lle(int64_t n, int64_t nnz, const int64_t *row_ptr, const 
     lle_edge_values(n, row_ptr, w, va.data());
     const CsrT T = transpose_csr(n, nnz, row_ptr, col, va.data());
     if (upload_csr(H, "lle", n, nnz, row_ptr, col, va.data(), &T)) return H.err;
-    // c >= sigma_max(I - P)^2 by power iteration on N^T N (at most 60 steps), with a 5 % margin
-    const double est = power_iteration(H, 0.61, 7.31, 60, 8, 1e-4, false, [&](float *X2, float *t) {
-        apply_sym_op(H, 2, 1.0f, X2, 2, 1, t, 1, X2 + 1, 2, 1.0f, nullptr, 0, 0.f, nullptr, 0);            // z = N^T N x
-    });
+    const double c = lle_shift_estimate(H);
     if (H.err) return H.err;
-    const double c = est > 0.0 ? est * 1.05 : 4.0;
     H.beta = (float)c;
     std::vector<float> sig(k);
     // (large graphs: the Chebyshev-filtered eigen-path on N^T N itself (kind 2), which converges where the block-Krylov solver runs out of its

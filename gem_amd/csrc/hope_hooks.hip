@@ -1,6 +1,7 @@
 // hope_hooks.hip -- what the library exports around the HOPE solvers for tests and tools: the host eigensolver's setters and wrappers, the three
-// building-block entry points (gemhip_hope_spmm / _gram / _tsgemm) and the eleven gemhip_test_hope_* hooks.  No kernel here: every hook calls the
-// launch function of hope_ops.hpp that the solvers call, on a local Hope.  Touching a hook recompiles this unit alone.
+// building-block entry points (gemhip_hope_spmm / _gram / _tsgemm) and the fourteen gemhip_test_hope_* hooks: ten on the launch functions, four on
+// what the solvers and set-ups compose of them (apply_S / apply_ST, cheb_filter, orth / orth_scaled, the two spectrum estimates).  No kernel here:
+// every hook calls the function of hope_ops.hpp that the solvers call, on a local Hope.  Touching a hook recompiles this unit alone.
 #include "hope_ops.hpp"
 #include "sym_eig.hpp"
 
@@ -275,4 +276,82 @@ extern "C" int gemhip_test_hope_randn(int64_t n, int32_t b, int32_t ld, uint64_t
     hook_upload(H, dX, X_inout, ld);
     randn(H, dX, b, ld, seed);
     return hook_download(H, X_inout, dX, (size_t)n * ld * sizeof(float));
+}
+
+// ------------------------------------------------------------------ test hooks, one layer up: what the solvers compose of the launch functions
+// apply_S (transpose = 0) / apply_ST (transpose = 1) of the operator `mode` (Hope::mode; `beta` is Hope::beta: the Katz factor, or c of mode 2) on the
+// CSR matrix as given: Out[:, :b] = S X or S^T X.  T0, T1 and W0 (n x ldt each) are the hook's own.
+extern "C" int gemhip_test_hope_apply_s(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t mode, float beta,
+                                        int32_t transpose, int32_t terms, int32_t b, const float *X_host, int32_t ldx, int32_t ldt, float *Out_inout,
+                                        int32_t ldo)
+{
+    GEMHIP_REQUIRE(hook_csr_ok(n, nnz, row_ptr, col), "test_hope_apply_s: bad CSR arguments");
+    GEMHIP_REQUIRE(mode >= 0 && mode <= 2 && (transpose == 0 || transpose == 1) && terms >= 0 && terms <= 400, "test_hope_apply_s: bad operator arguments");
+    GEMHIP_REQUIRE(X_host && Out_inout && b >= 1 && b <= 512 && ldx >= b && ldt >= b && ldo >= b, "test_hope_apply_s: bad block arguments");
+    Hope H;
+    upload_csr_w(H, n, nnz, row_ptr, col, w, true);
+    H.mode = mode; H.beta = beta;
+    DevBuf<float> dX, dO, dT[3];                                              // T0, T1, W0
+    hook_upload(H, dX, X_host, ldx); hook_upload(H, dO, Out_inout, ldo);
+    for (DevBuf<float> &t : dT) { HOPE_TRY(H, t.reserve((size_t)n * ldt)); HOPE_TRY(H, hipMemsetAsync(t, 0, (size_t)n * ldt * sizeof(float), H.s)); }
+    if (transpose) apply_ST(H, dX, ldx, b, terms, dT[0], dT[1], ldt, dO, ldo);
+    else apply_S(H, dX, ldx, b, terms, dT[0], dT[1], dT[2], ldt, dO, ldo);
+    return hook_download(H, Out_inout, dO, (size_t)n * ldo * sizeof(float));
+}
+
+// cheb_filter: V[:, :cols] <- T_m((Op - c I) / e) V[:, :cols], Op of `kind` (0: the CSR matrix; 2: (I - A)^T (I - A)) as in gemhip_test_hope_sym_op, with
+// Q[:, :nl] (NULL when nl = 0) projected out of the two live terms every q degrees.  The three recurrence blocks and the kind-2 scratch (n x ldf) are the hook's own.
+extern "C" int gemhip_test_hope_cheb_filter(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t kind, int32_t m,
+                                            double c, double e, float *V_inout, int32_t ldv, int32_t cols, int32_t ldf, const float *Q_host, int32_t ldq,
+                                            int32_t nl, int32_t q)
+{
+    GEMHIP_REQUIRE(hook_csr_ok(n, nnz, row_ptr, col), "test_hope_cheb_filter: bad CSR arguments");
+    GEMHIP_REQUIRE((kind == 0 || kind == 2) && m >= 1 && m <= 1024 && e > 0.0 && std::isfinite(c) && std::isfinite(e), "test_hope_cheb_filter: bad filter arguments");
+    GEMHIP_REQUIRE(V_inout && cols >= 1 && cols <= 512 && ldv >= cols && ldf >= cols, "test_hope_cheb_filter: bad block arguments");
+    GEMHIP_REQUIRE(nl >= 0 && q >= 0 && (nl == 0 || (Q_host && ldq >= nl)), "test_hope_cheb_filter: bad locked block");
+    Hope H;
+    upload_csr_w(H, n, nnz, row_ptr, col, w, true);
+    H.mode = kind;
+    DevBuf<float> dV, dQ, dF[4];                                              // F[0..2], Ts
+    hook_upload(H, dV, V_inout, ldv);
+    if (nl > 0) hook_upload(H, dQ, Q_host, ldq);
+    for (DevBuf<float> &f : dF) { HOPE_TRY(H, f.reserve((size_t)n * ldf)); HOPE_TRY(H, hipMemsetAsync(f, 0, (size_t)n * ldf * sizeof(float), H.s)); }
+    float *const F[3] = {dF[0].get(), dF[1].get(), dF[2].get()};
+    cheb_filter(H, kind, dV, ldv, cols, m, c, e, F, ldf, dF[3], dQ, ldq, nl, q);
+    return hook_download(H, V_inout, dV, (size_t)n * ldv * sizeof(float));
+}
+
+// orth (scaled = 0: tol, abs_floor, passes as the solvers pass them) or orth_scaled (scaled = 1: passes) on Y[:, :b] in place through an n x ldt scratch;
+// keep_out receives the number of columns kept (columns [0, keep) of Y are the orthonormal block; the columns behind them keep what they held).
+extern "C" int gemhip_test_hope_orth(int64_t n, float *Y_inout, int32_t ld, int32_t b, int32_t ldt, int32_t scaled, double tol, double abs_floor,
+                                     int32_t passes, int32_t *keep_out)
+{
+    GEMHIP_REQUIRE(n >= 1 && Y_inout && keep_out && b >= 1 && b <= 512 && ld >= b && ldt >= b && passes >= 1 && passes <= 4 && (scaled == 0 || scaled == 1),
+                   "test_hope_orth: bad arguments");
+    Hope H; H.n = n;
+    DevBuf<float> dY, dT;
+    hook_upload(H, dY, Y_inout, ld);
+    HOPE_TRY(H, dT.reserve((size_t)n * ldt));
+    HOPE_TRY(H, hipMemsetAsync(dT, 0, (size_t)n * ldt * sizeof(float), H.s));
+    const int keep = scaled ? orth_scaled(H, dY, ld, b, dT, ldt, passes) : orth(H, dY, ld, b, dT, ldt, tol, abs_floor, passes);
+    *keep_out = H.err ? 0 : keep;
+    return hook_download(H, Y_inout, dY, (size_t)n * ld * sizeof(float));
+}
+
+// The spectrum estimates of the set-ups.  which = 0: the rho hope_setup ends with for the CSR matrix as given (katz_rho_estimate: margin and cap
+// applied).  which = 1: the c gemhip_lle ends with (lle_shift_estimate) -- the rows are l1-normalised here as gemhip_lle normalises them.
+extern "C" int gemhip_test_hope_spectrum_estimate(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t which,
+                                                  double *estimate_out)
+{
+    GEMHIP_REQUIRE(hook_csr_ok(n, nnz, row_ptr, col), "test_hope_spectrum_estimate: bad CSR arguments");
+    GEMHIP_REQUIRE((which == 0 || which == 1) && estimate_out, "test_hope_spectrum_estimate: bad arguments");
+    Hope H;
+    std::vector<float> va(std::max<int64_t>(nnz, 1), 1.0f);
+    if (which == 1) lle_edge_values(n, row_ptr, w, va.data());
+    else if (w) std::copy(w, w + nnz, va.begin());
+    upload_csr_w(H, n, nnz, row_ptr, col, va.data(), true);
+    if (which == 1) H.mode = 2;
+    const double est = which == 0 ? katz_rho_estimate(H, row_ptr, col, va.data()) : lle_shift_estimate(H);
+    if (!H.err) *estimate_out = est;
+    return H.err;
 }

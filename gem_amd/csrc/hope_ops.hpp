@@ -76,6 +76,17 @@ void reset_solve_stats(Hope &H);
 int solve_operator(Hope &H, bool symmetric, int32_t k, int32_t oversample, int32_t krylov_steps, int32_t max_restarts, float tol, uint64_t seed,
                    int terms, double br, int out_mode, float *U_sqrtS, float *V_sqrtS, float *sigma, double *stats);
 
+// The solvers' own compositions, shared with their test hooks (definitions and contracts in hope_solve.hip)
+int orth(Hope &H, float *Y, int ld, int b, float *Tmp, int ldt, double tol, double abs_floor = 0.0, int passes = 2, bool *remixed = nullptr);
+int orth_scaled(Hope &H, float *Y, int ld, int b, float *Tmp, int ldt, int passes);
+void cheb_filter(Hope &H, int kind, float *V, int ldv, int cols, int m, double c, double e, float *const F[3], int ldf, float *Ts, const float *Q, int ldq,
+                 int nl, int q);
+
+// ---------------------------------------------------------------------- the set-up estimates (hope.hip), shared with their test hook
+// Both run power_iteration (below) on the operator H holds (A and A^T uploaded) and apply the margin the set-up relies on.
+double katz_rho_estimate(Hope &H, const int64_t *row_ptr, const int32_t *col, const float *va);     // >= sigma_max(A): hope_setup's rho, margin and cap applied
+double lle_shift_estimate(Hope &H);                                                                   // >= sigma_max(I - P)^2: gemhip_lle's c (H holds P, P^T)
+
 // The device half of orth() / orth_scaled(): per pass the Gram matrix of the block's columns comes in, host_pass(keep, G, C) turns it into the
 // keep x nk coefficients, and Y <- Y C goes out through Tmp.  Returns the number of columns kept.
 template <typename HostPass>

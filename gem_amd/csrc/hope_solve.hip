@@ -8,12 +8,13 @@
 
 using namespace gemhip;
 
-namespace {
+// orth, orth_scaled and cheb_filter are declared in hope_ops.hpp: the solvers below call them, and so do their test hooks (hope_hooks.hip).
+namespace gemhip {
 
 // Orthonormalise the b columns of Y (n x b, ld) in place (Tmp = scratch).  Well-conditioned blocks take a
 // CholeskyQR step (Y <- Y R^-1); otherwise the Gram eigen-decomposition Y <- Y W L^-1/2 drops directions whose
 // relative energy is below `tol` or whose absolute energy is below `abs_floor` (rank revealing: orth_pass).  Two passes.
-int orth(Hope &H, float *Y, int ld, int b, float *Tmp, int ldt, double tol, double abs_floor = 0.0, int passes = 2, bool *remixed = nullptr)
+int orth(Hope &H, float *Y, int ld, int b, float *Tmp, int ldt, double tol, double abs_floor, int passes, bool *remixed)
 {
     return orth_passes(H, Y, ld, b, Tmp, ldt, passes, [&](int keep, std::vector<double> &G, std::vector<double> &C) {
         const int nk = orth_pass(keep, G, tol, abs_floor, C, remixed);
@@ -21,6 +22,10 @@ int orth(Hope &H, float *Y, int ld, int b, float *Tmp, int ldt, double tol, doub
         return nk;
     });
 }
+
+}  // namespace gemhip
+
+namespace {
 
 // ------------------------------------------------------------------- what both solvers end with
 // The compact [n][k] block Tmp goes to the caller's n x k output
@@ -213,6 +218,10 @@ int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t krylov
 // relative must not be amplified past the wanted ones; 1e4 per cycle).  Against the block-Krylov path on S^T S this needs ~7x fewer
 // SpMM columns, no n x 512 basis and no 512 x 512 projected eigenproblem (measured: DESIGN.md 3.2).
 
+}  // namespace
+
+namespace gemhip {
+
 // CholeskyQR on the column-NORMALISED Gram matrix, with the scaled Gram's eigen-decomposition as the fallback (orth_scaled_pass)
 int orth_scaled(Hope &H, float *Y, int ld, int b, float *Tmp, int ldt, int passes)
 {
@@ -246,6 +255,10 @@ void cheb_filter(Hope &H, int kind, float *V, int ldv, int cols, int m, double c
     }
     HOPE_TRY(H, hipMemcpy2DAsync(V, (size_t)ldv * sizeof(float), F[i1], (size_t)ldf * sizeof(float), (size_t)cols * sizeof(float), H.n, hipMemcpyDeviceToDevice, H.s));
 }
+
+}  // namespace gemhip
+
+namespace {
 
 // Returns H.err; *fell_back = true when the iteration broke down or did not converge in max_cycles (the caller then runs the
 // general block-Krylov solver); outputs are only written on success.

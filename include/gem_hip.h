@@ -539,6 +539,29 @@ int gemhip_test_hope_lincomb(int64_t n, int32_t b, float a, const float *X_host,
                              int32_t ldo);
 int gemhip_test_hope_randn(int64_t n, int32_t b, int32_t ld, uint64_t seed, float *X_inout);
 
+/* One layer up: what the solvers and the set-ups compose of those launch functions (hope_ops.hip apply_S / apply_ST, hope_solve.hip
+ * cheb_filter / orth / orth_scaled, hope.hip katz_rho_estimate / lle_shift_estimate).  Same conventions: the CSR matrix is used as given
+ * (with its transpose built as the entry points build it), *_inout blocks travel whole, scratch blocks are the hook's own.
+ *   apply_s          : Out[:, :b] = S X (transpose 0, apply_S) or S^T X (transpose 1, apply_ST).  mode 0: S = sum_{t=1..terms+1} (beta A)^t;
+ *                      mode 1: S = I + A; mode 2: S = beta I - (I - A)^T (I - A) (`terms` unused in modes 1 and 2).  T0, T1, W0: n x ldt.
+ *   cheb_filter      : V[:, :cols] <- T_m((Op - c I) / e) V[:, :cols], Op of `kind` as in sym_op (0 or 2); with nl > 0 the columns Q[:, :nl] are
+ *                      projected out of the two live terms of the recurrence every q degrees.  The recurrence blocks are n x ldf.
+ *   orth             : scaled 0: orth(Y, b, tol, abs_floor, passes); scaled 1: orth_scaled(Y, b, passes) (tol, abs_floor unused), in place through an
+ *                      n x ldt scratch.  keep_out: the columns kept, [0, keep) of Y; the columns behind them keep what they held.
+ *   spectrum_estimate: which 0: the rho hope_setup derives beta x sigma_max and the Katz term count from (power iteration on A^T A, x 1.1, capped by
+ *                      the absolute row / column sums); which 1: the shift c gemhip_lle uses (power iteration on (I - P)^T (I - P), x 1.05), with the
+ *                      rows l1-normalised here as gemhip_lle normalises them. */
+int gemhip_test_hope_apply_s(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t mode, float beta,
+                             int32_t transpose, int32_t terms, int32_t b, const float *X_host, int32_t ldx, int32_t ldt, float *Out_inout,
+                             int32_t ldo);
+int gemhip_test_hope_cheb_filter(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t kind, int32_t m,
+                                 double c, double e, float *V_inout, int32_t ldv, int32_t cols, int32_t ldf, const float *Q_host, int32_t ldq,
+                                 int32_t nl, int32_t q);
+int gemhip_test_hope_orth(int64_t n, float *Y_inout, int32_t ld, int32_t b, int32_t ldt, int32_t scaled, double tol, double abs_floor,
+                          int32_t passes, int32_t *keep_out);
+int gemhip_test_hope_spectrum_estimate(int64_t n, int64_t nnz, const int64_t *row_ptr, const int32_t *col, const float *w, int32_t which,
+                                       double *estimate_out);
+
 /* -------------------------------------------------- evaluation
  * Average precision of graph reconstruction for SAMPLED nodes, with the exact semantics of
  * gem/evaluation/metrics.py:27-46 (computeMAP) over the candidate list of

@@ -12,7 +12,8 @@ def _orth_scaled(Y, passes):
     """CholeskyQR on the column-normalised Gram matrix; eigen fallback drops directions below 1e-6 relative energy (orth_scaled)."""
     for _ in range(passes):
         G = (Y.T @ Y).astype(np.float64)
-        d = 1.0 / np.sqrt(np.maximum(np.diag(G), 1e-300))
+        g = np.diag(G)
+        d = np.where(g > 0, 1.0 / np.sqrt(np.where(g > 0, g, 1.0)), 0.0)          # a zero column: dinv = 0, as in normalise_gram (hope_host.hip)
         G = G * d[:, None] * d[None, :]
         try:
             R = np.linalg.cholesky(G).T
