@@ -110,6 +110,10 @@ _SIGS = {
     'gemhip_eval_ap': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, i32p, f64p]),
     'gemhip_eval_pairs': (C.c_int, [C.c_void_p, C.c_int64, i32p, i32p, f64p, C.POINTER(C.c_uint8)]),
     'gemhip_eval_last_pairs_ms': (C.c_int, [C.c_void_p, f64p]),
+    'gemhip_eval_set_mask': (C.c_int, [C.c_void_p, i64p, i32p]),
+    'gemhip_eval_ap_masked': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, i32p, f64p, i64p]),
+    'gemhip_eval_topk': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, i32p, C.c_int32, i32p, f64p, C.POINTER(C.c_uint8)]),
+    'gemhip_eval_last_kernel_ms': (C.c_int, [C.c_void_p, f64p]),
     'gemhip_eval_destroy': (C.c_int, [C.c_void_p]),
     'gemhip_n2v_train': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_uint64, C.c_int32, f32p, f64p]),

@@ -23,9 +23,13 @@
 //   gemhip_eval_ap     the AP kernel above for sampled nodes;
 //   gemhip_eval_pairs  score + "is (st -> ed) an edge" for an explicit pair list: the reference's pair-sampled MAP / precision curve
 //                      (evaluation_util.py:5-26) and, over the edge list, its weighted reconstruction error (evaluate_graph_reconstruction.py:38-42).
+// and, with a second graph as a mask (gemhip_eval_set_mask: the TRAIN graph of a link-prediction split, the handle's CSR being the TEST graph):
+//   gemhip_eval_ap_masked  the same AP with the training arcs taken out of every candidate list;
+//   gemhip_eval_topk       every sampled node's k best candidates, in the evaluator's order.
 #include "common.hpp"
 #include <algorithm>
 #include <climits>
+#include <utility>
 #include <vector>
 
 using namespace gemhip;
@@ -116,6 +120,189 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_ap_kernel(int64_t n, int da, co
     for (int k = threadIdx.x; k < nnb; k += EV_BLOCK) { s_out[off + k] = s_nb[k]; cnt_out[off + k] = cnt_nb[k]; }
 }
 
+// ---- link prediction: the handle's CSR is the TEST graph, a second CSR (the TRAIN graph, rows sorted and de-duplicated by
+// gemhip_eval_set_mask) removes candidates: j is a candidate of i only if (i -> j) is not a training arc.  A wavefront visits its j in
+// ascending order, so it walks ONE cursor through the sorted mask row of i -- the row stays in global memory, however long (a hub's
+// training neighbours), and the entry under the cursor is kept in a register: a row that is not masked costs one integer compare.
+struct MaskWalk {
+    const int32_t *p, *end; int cur;                               // cur = *p, or INT_MAX past the end (every j is < n <= INT_MAX)
+    __device__ __forceinline__ void open(const int64_t *__restrict__ mask_row_ptr, const int32_t *__restrict__ mask_col, int i, int64_t first)
+    {
+        p = end = nullptr; cur = INT_MAX;
+        if (!mask_row_ptr) return;
+        const int32_t *lo = mask_col + mask_row_ptr[i], *hi = mask_col + mask_row_ptr[i + 1];
+        end = hi;
+        while (lo < hi) { const int32_t *mid = lo + ((hi - lo) >> 1); if (*mid < first) lo = mid + 1; else hi = mid; }     // entries below `first` are never asked for
+        p = lo; cur = p < end ? *p : INT_MAX;
+    }
+    __device__ __forceinline__ bool masked(int64_t j)              // j never decreases between calls
+    {
+        while (cur < j) { ++p; cur = p < end ? *p : INT_MAX; }
+        return cur == j;
+    }
+};
+
+// A_i in registers and the fp64 score of a row of B, in eval_ap_kernel's own arithmetic (same lane-to-column map, same order of the sums).
+template <int NV, int KIND>
+struct RowScore {
+    float a[NV]; const float *B; int ldb, da, lane;
+    __device__ __forceinline__ RowScore(const float *__restrict__ A, const float *__restrict__ B_, int ldb_, int da_, int i) : B(B_), ldb(ldb_), da(da_), lane(lane_id())
+    {
+#pragma unroll
+        for (int c = 0; c < NV; ++c) { const int cc = c * WAVE + lane; a[c] = cc < da ? A[(int64_t)i * ldb + cc] : 0.f; }
+    }
+    __device__ __forceinline__ double operator()(int64_t j) const
+    {
+        double part = 0.0;
+        const float *bj = B + j * ldb;
+#pragma unroll
+        for (int c = 0; c < NV; ++c) { const int cc = c * WAVE + lane; if (cc < da) part += term<KIND>(a[c], bj[cc]); }
+        return finish_score<KIND>(wave_sum_f64(part));
+    }
+};
+
+// eval_ap_kernel with the mask applied in the stream.  The chunks hold the POSITIVES of i (its test neighbours that are not masked; the host
+// removes the masked ones), and rank_all counts unmasked candidates only.  mask_row_ptr == nullptr: no mask, the counts of eval_ap_kernel.
+template <int NV, int KIND>
+__global__ __launch_bounds__(EV_BLOCK) void eval_ap_masked_kernel(int64_t n, int da, const float *__restrict__ A, const float *__restrict__ B, int ldb,
+                                                                  int undirected, const int32_t *__restrict__ chunk_node, const int64_t *__restrict__ chunk_off,
+                                                                  const int32_t *__restrict__ chunk_cnt, const int32_t *__restrict__ nb,
+                                                                  const int64_t *__restrict__ mask_row_ptr, const int32_t *__restrict__ mask_col,
+                                                                  double *__restrict__ s_out, int32_t *__restrict__ cnt_out)
+{
+    __shared__ double s_nb[EV_MAXNB];
+    __shared__ int t_nb[EV_MAXNB];
+    __shared__ int cnt_nb[EV_MAXNB];
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // in a scalar register: j and the mask cursor stay scalar
+    const int i = chunk_node[blockIdx.x];
+    const int64_t off = chunk_off[blockIdx.x];
+    const int nnb = chunk_cnt[blockIdx.x];
+    for (int k = threadIdx.x; k < EV_MAXNB; k += EV_BLOCK) { cnt_nb[k] = 0; t_nb[k] = k < nnb ? nb[off + k] : -1; }
+    __syncthreads();
+    const RowScore<NV, KIND> score(A, B, ldb, da, i);
+    for (int k = wave; k < nnb; k += EV_BLOCK / WAVE) {
+        const double s = score(t_nb[k]);
+        if (lane == 0) s_nb[k] = s;
+    }
+    __syncthreads();
+    double my_s[EV_NREG]; int my_t[EV_NREG]; int my_c[EV_NREG];
+#pragma unroll
+    for (int r = 0; r < EV_NREG; ++r) {
+        const int k = r * WAVE + lane;
+        my_s[r] = k < nnb ? s_nb[k] : 0.0; my_t[r] = k < nnb ? t_nb[k] : -1; my_c[r] = 0;
+    }
+    const int64_t lo = undirected ? (int64_t)i + 1 : 0;
+    const int nreg_used = (nnb + WAVE - 1) / WAVE;
+    MaskWalk mask;
+    mask.open(mask_row_ptr, mask_col, i, lo);
+    for (int64_t j = lo + wave; j < n; j += EV_BLOCK / WAVE) {
+        if (j == i || mask.masked(j)) continue;
+        const double s = score(j);
+        if (!(s > 0.0)) continue;
+#pragma unroll
+        for (int r = 0; r < EV_NREG; ++r)
+            if (r < nreg_used) my_c[r] += (s > my_s[r] || (s == my_s[r] && j < my_t[r])) ? 1 : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < EV_NREG; ++r) {
+        const int k = r * WAVE + lane;
+        if (k < nnb && my_c[r]) atomicAdd(&cnt_nb[k], my_c[r]);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < nnb; k += EV_BLOCK) { s_out[off + k] = s_nb[k]; cnt_out[off + k] = cnt_nb[k]; }
+}
+
+// ---- per-node top-k: one workgroup per sampled node, the same row stream and mask walk.  Every wavefront keeps the k best of the rows IT
+// saw, unsorted, in its own slice of LDS (12 k bytes; 48 KiB per workgroup at k = 1024, three workgroups per CU), behind a running threshold:
+// the entry that ranks LAST among the kept ones.  Lane l owns slots l, l + 64, ... and keeps the last-ranked of its own slots in registers, so a
+// row below the threshold costs one compare, and a row that enters replaces the threshold entry: the owner rescans its <= 16 slots, one butterfly
+// finds the new threshold.  The order is total (score descending, node id ascending; ids are distinct), so the k best of the union of the four
+// lists are the node's k best, and each entry's place is the number of entries that rank before it -- counted, not sorted: no atomics, and
+// the same bytes whatever the wavefronts' timing.  Only k values per wavefront are ever held: no nsample x n matrix.
+constexpr int TK_MAXK = 1024;
+constexpr int TK_WAVES = EV_BLOCK / WAVE;
+
+__device__ __forceinline__ bool ranks_before(double sa, int ia, double sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
+
+// The last-ranked of the lanes' (s, id, slot); slot < 0: the lane holds nothing.  Every lane ends with the same triple.
+__device__ __forceinline__ void wave_last_ranked(double &s, int &id, int &slot)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double os = __shfl_xor(s, o); const int oi = __shfl_xor(id, o), osl = __shfl_xor(slot, o);
+        if (osl >= 0 && (slot < 0 || ranks_before(s, id, os, oi))) { s = os; id = oi; slot = osl; }
+    }
+}
+
+template <int NV, int KIND>
+__global__ __launch_bounds__(EV_BLOCK) void eval_topk_kernel(int64_t n, int da, const float *__restrict__ A, const float *__restrict__ B, int ldb, int undirected,
+                                                             const int32_t *__restrict__ nodes, int k, const int64_t *__restrict__ mask_row_ptr,
+                                                             const int32_t *__restrict__ mask_col, const int64_t *__restrict__ row_ptr,
+                                                             const int32_t *__restrict__ col, int32_t *__restrict__ id_out, double *__restrict__ score_out,
+                                                             uint8_t *__restrict__ hit_out)
+{
+    extern __shared__ double tk_lds[];                             // [TK_WAVES][k] scores, then [TK_WAVES][k] ids
+    __shared__ int w_cnt[TK_WAVES];
+    double *const s_all = tk_lds; int *const id_all = reinterpret_cast<int *>(tk_lds + TK_WAVES * k);
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // in a scalar register: j and the mask cursor stay scalar
+    const int i = nodes[blockIdx.x];
+    double *const ls = s_all + wave * k; int *const li = id_all + wave * k;
+    const RowScore<NV, KIND> score(A, B, ldb, da, i);
+    const int64_t lo = undirected ? (int64_t)i + 1 : 0;
+    MaskWalk mask;
+    mask.open(mask_row_ptr, mask_col, i, lo);
+    int cnt = 0;                                                   // kept entries of this wavefront (wave-uniform)
+    double my_s = 0.0; int my_id = -1, my_slot = -1;               // the last-ranked of this lane's own slots
+    double th_s = 0.0; int th_id = -1, th_slot = -1;               // the wavefront's threshold entry, valid once cnt == k
+    for (int64_t j = lo + wave; j < n; j += TK_WAVES) {
+        if (j == i || mask.masked(j)) continue;
+        const double s = score(j);
+        if (!(s > 0.0)) continue;
+        if (cnt < k) {
+            if (lane == (cnt & (WAVE - 1))) {
+                ls[cnt] = s; li[cnt] = (int)j;
+                if (my_slot < 0 || ranks_before(my_s, my_id, s, (int)j)) { my_s = s; my_id = (int)j; my_slot = cnt; }
+            }
+            if (++cnt == k) { th_s = my_s; th_id = my_id; th_slot = my_slot; wave_last_ranked(th_s, th_id, th_slot); }
+            continue;
+        }
+        if (!ranks_before(s, (int)j, th_s, th_id)) continue;
+        if (lane == (th_slot & (WAVE - 1))) {
+            ls[th_slot] = s; li[th_slot] = (int)j;
+            my_slot = -1;
+            for (int q = lane; q < k; q += WAVE) {
+                const double qs = ls[q]; const int qi = li[q];
+                if (my_slot < 0 || ranks_before(my_s, my_id, qs, qi)) { my_s = qs; my_id = qi; my_slot = q; }
+            }
+        }
+        th_s = my_s; th_id = my_id; th_slot = my_slot;
+        wave_last_ranked(th_s, th_id, th_slot);
+    }
+    if (lane == 0) w_cnt[wave] = cnt;
+    __syncthreads();
+    // ---- merge: the place of an entry = the number of kept entries (all wavefronts) that rank before it
+    int total = 0;
+    for (int w = 0; w < TK_WAVES; ++w) total += w_cnt[w];
+    const int64_t out = (int64_t)blockIdx.x * k;
+    for (int e = threadIdx.x; e < TK_WAVES * k; e += EV_BLOCK) {
+        const int w = e / k;
+        if (e - w * k >= w_cnt[w]) continue;
+        const double s = s_all[e]; const int id = id_all[e];
+        int rank = 0;
+        for (int w2 = 0; w2 < TK_WAVES; ++w2) {
+            const double *s2 = s_all + w2 * k; const int *id2 = id_all + w2 * k;
+            const int c2 = w_cnt[w2];
+            for (int q = 0; q < c2; ++q) rank += ranks_before(s2[q], id2[q], s, id) ? 1 : 0;
+        }
+        if (rank >= k) continue;
+        int64_t lo_e = row_ptr[i], hi_e = row_ptr[i + 1];          // is (i -> id) a test arc: eval_pairs_kernel's search, columns sorted
+        const int64_t end_e = hi_e;
+        while (lo_e < hi_e) { const int64_t mid = lo_e + ((hi_e - lo_e) >> 1); if (col[mid] < id) lo_e = mid + 1; else hi_e = mid; }
+        id_out[out + rank] = id; score_out[out + rank] = s; hit_out[out + rank] = (lo_e < end_e && col[lo_e] == id) ? 1 : 0;
+    }
+    for (int r = (total < k ? total : k) + threadIdx.x; r < k; r += EV_BLOCK) { id_out[out + r] = -1; score_out[out + r] = 0.0; hit_out[out + r] = 0; }
+}
+
 // ---- pair scoring: a 16-lane group per (st, ed); one row of A and one of B are gathered per pair (2*4*d bytes), nothing is reused, so the kernel
 // is a pure row gather.  Four pairs per wavefront keep all 64 lanes busy at d <= 64 and four times as many rows in flight as a wavefront per pair.
 // VEC (ld % 4 == 0: every row starts on 16 bytes): lane s of the group loads the float4 at columns 4*(16c + s), c < NV; the tail float4 of a row
@@ -187,7 +374,10 @@ struct gemhip_eval {
     std::vector<int64_t> row_ptr; std::vector<int32_t> col;          // host copy: the AP call cuts the sampled nodes' rows into chunks
     DevBuf<float> A, B; DevBuf<int64_t> d_row_ptr; DevBuf<int32_t> d_col;
     DevBuf<int32_t> d_st, d_ed; DevBuf<double> d_score; DevBuf<uint8_t> d_hit;     // pair scratch, grow-only
-    double last_pairs_ms = 0.0;
+    bool has_mask = false;                                           // link prediction: the train graph, rows sorted and de-duplicated
+    std::vector<int64_t> mask_row_ptr; std::vector<int32_t> mask_col;
+    DevBuf<int64_t> d_mask_row_ptr; DevBuf<int32_t> d_mask_col;
+    double last_pairs_ms = 0.0, last_kernel_ms = 0.0;
     const float *dB() const { return B ? B.get() : A.get(); }
 };
 
@@ -229,22 +419,49 @@ extern "C" int gemhip_eval_destroy(gemhip_eval_t h)
     return GEMHIP_OK;
 }
 
-extern "C" int gemhip_eval_ap(gemhip_eval_t h, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out)
+namespace {
+
+// Runs `launch` between two HIP events on the null stream, waits for it and stores the device time in *ms.
+template <typename Launch>
+hipError_t timed_launch(double *ms, Launch launch)
 {
-    GEMHIP_REQUIRE(h && nsample >= 0 && (nsample == 0 || (nodes && ap_out)), "eval_ap: bad arguments");
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e != hipSuccess) return e;
+    e = hipEventCreate(&e1);
+    if (e != hipSuccess) { (void)hipEventDestroy(e0); return e; }
+    (void)hipEventRecord(e0, 0);
+    launch();
+    e = hipGetLastError();
+    (void)hipEventRecord(e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float t = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (e == hipSuccess) *ms = t;
+    return e;
+}
+
+// gemhip_eval_ap (masked = false: eval_ap_kernel, the handle's mask is ignored) and gemhip_eval_ap_masked (eval_ap_masked_kernel).
+int ap_impl(gemhip_eval_t h, const char *who, bool masked, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out, int64_t *npos_out)
+{
+    GEMHIP_REQUIRE(h && nsample >= 0 && (nsample == 0 || (nodes && ap_out)), "%s: bad arguments", who);
     if (nsample == 0) return GEMHIP_OK;
     const int64_t n = h->n;
     const int64_t *row_ptr = h->row_ptr.data(); const int32_t *col = h->col.data();
-    for (int64_t k = 0; k < nsample; ++k) GEMHIP_REQUIRE(nodes[k] >= 0 && nodes[k] < n, "eval_ap: node %d outside [0,%lld)", nodes[k], (long long)n);
-    // ---- candidate true neighbours of every sampled node (j != i, j > i when undirected, each once), cut into chunks
+    for (int64_t k = 0; k < nsample; ++k) GEMHIP_REQUIRE(nodes[k] >= 0 && nodes[k] < n, "%s: node %d outside [0,%lld)", who, nodes[k], (long long)n);
+    const bool use_mask = masked && h->has_mask;
+    // ---- candidate true neighbours of every sampled node (j != i, j > i when undirected, not a mask arc, each once), cut into chunks
     std::vector<int32_t> nb, chunk_node, chunk_cnt; std::vector<int64_t> chunk_off, node_off(nsample + 1, 0);
     std::vector<int32_t> tmp;
     for (int64_t k = 0; k < nsample; ++k) {
         const int i = nodes[k];
         tmp.clear();
+        const int32_t *mb = use_mask ? h->mask_col.data() + h->mask_row_ptr[i] : nullptr, *me = use_mask ? h->mask_col.data() + h->mask_row_ptr[i + 1] : nullptr;
         for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
             const int t = col[e];
             if (t == i || (undirected && t < i)) continue;
+            if (use_mask && std::binary_search(mb, me, t)) continue;
             tmp.push_back(t);
         }
         std::sort(tmp.begin(), tmp.end());
@@ -258,23 +475,27 @@ extern "C" int gemhip_eval_ap(gemhip_eval_t h, int32_t undirected, int64_t nsamp
     }
     const int64_t nchunk = (int64_t)chunk_node.size(), total = (int64_t)nb.size();
     std::vector<double> s_host(std::max<int64_t>(total, 1)); std::vector<int32_t> cnt_host(std::max<int64_t>(total, 1));
+    h->last_kernel_ms = 0.0;
     if (nchunk > 0) {
         DevBuf<int32_t> dnb, dcn, dcc, dcnt; DevBuf<int64_t> dco; DevBuf<double> ds;
         const float *dA = h->A, *dB = h->dB();
         const int da = h->da, ld = h->ld;
+        const int64_t *dmrp = use_mask ? h->d_mask_row_ptr.get() : nullptr; const int32_t *dmcol = use_mask ? h->d_mask_col.get() : nullptr;
         GEMHIP_CHECK(dnb.upload(nb.data(), total));
         GEMHIP_CHECK(dcn.upload(chunk_node.data(), nchunk));
         GEMHIP_CHECK(dcc.upload(chunk_cnt.data(), nchunk));
         GEMHIP_CHECK(dco.upload(chunk_off.data(), nchunk));
         GEMHIP_CHECK(ds.reserve(total)); GEMHIP_CHECK(dcnt.reserve(total));
         const int nv = (da + WAVE - 1) / WAVE;
-#define EV_LAUNCH(NV, KIND) hipLaunchKernelGGL((eval_ap_kernel<NV, KIND>), dim3((unsigned)nchunk), dim3(EV_BLOCK), 0, 0, n, da, dA, dB, ld, (int)undirected, \
-                                               dcn.get(), dco.get(), dcc.get(), dnb.get(), ds.get(), dcnt.get())
+#define EV_LAUNCH(NV, KIND) do { \
+            if (masked) hipLaunchKernelGGL((eval_ap_masked_kernel<NV, KIND>), dim3((unsigned)nchunk), dim3(EV_BLOCK), 0, 0, n, da, dA, dB, ld, (int)undirected, \
+                                           dcn.get(), dco.get(), dcc.get(), dnb.get(), dmrp, dmcol, ds.get(), dcnt.get()); \
+            else hipLaunchKernelGGL((eval_ap_kernel<NV, KIND>), dim3((unsigned)nchunk), dim3(EV_BLOCK), 0, 0, n, da, dA, dB, ld, (int)undirected, \
+                                    dcn.get(), dco.get(), dcc.get(), dnb.get(), ds.get(), dcnt.get()); } while (0)
 #define EV_LAUNCH_NV(KIND) do { if (nv <= 1) EV_LAUNCH(1, KIND); else if (nv <= 2) EV_LAUNCH(2, KIND); else if (nv <= 4) EV_LAUNCH(4, KIND); else EV_LAUNCH(8, KIND); } while (0)
-        if (h->kind == 0) EV_LAUNCH_NV(0); else EV_LAUNCH_NV(1);
+        GEMHIP_CHECK(timed_launch(&h->last_kernel_ms, [&] { if (h->kind == 0) EV_LAUNCH_NV(0); else EV_LAUNCH_NV(1); }));
 #undef EV_LAUNCH_NV
 #undef EV_LAUNCH
-        GEMHIP_CHECK(hipGetLastError());
         GEMHIP_CHECK(hipMemcpy(s_host.data(), ds, total * 8, hipMemcpyDeviceToHost));
         GEMHIP_CHECK(hipMemcpy(cnt_host.data(), dcnt, total * 4, hipMemcpyDeviceToHost));
     }
@@ -288,7 +509,91 @@ extern "C" int gemhip_eval_ap(gemhip_eval_t h, int32_t undirected, int64_t nsamp
         double sum = 0.0;
         for (size_t r = 0; r < ord.size(); ++r) sum += (double)(r + 1) / (double)(1 + cnt_host[ord[r]]);
         ap_out[k] = ord.empty() ? 0.0 : sum / (double)ord.size();
+        if (npos_out) npos_out[k] = (int64_t)ord.size();
     }
+    return GEMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int gemhip_eval_ap(gemhip_eval_t h, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out)
+{
+    return ap_impl(h, "eval_ap", false, undirected, nsample, nodes, ap_out, nullptr);
+}
+
+extern "C" int gemhip_eval_set_mask(gemhip_eval_t h, const int64_t *mask_row_ptr, const int32_t *mask_col)
+{
+    GEMHIP_REQUIRE(h, "eval_set_mask: handle is null");
+    if (!mask_row_ptr) {                                             // clear
+        h->has_mask = false;
+        h->mask_row_ptr.clear(); h->mask_col.clear();
+        h->d_mask_row_ptr.reset(); h->d_mask_col.reset();
+        return GEMHIP_OK;
+    }
+    const int64_t n = h->n;
+    GEMHIP_REQUIRE(mask_row_ptr[0] == 0, "eval_set_mask: row_ptr[0] is %lld, not 0", (long long)mask_row_ptr[0]);
+    for (int64_t i = 0; i < n; ++i) GEMHIP_REQUIRE(mask_row_ptr[i + 1] >= mask_row_ptr[i], "eval_set_mask: row_ptr decreases at row %lld", (long long)i);
+    const int64_t nnz = mask_row_ptr[n];
+    GEMHIP_REQUIRE(nnz == 0 || mask_col, "eval_set_mask: col is null");
+    for (int64_t e = 0; e < nnz; ++e) GEMHIP_REQUIRE(mask_col[e] >= 0 && mask_col[e] < n, "eval_set_mask: column %d outside [0,%lld)", mask_col[e], (long long)n);
+    // ---- the kernels walk a cursor through a row: ascending, each column once
+    std::vector<int64_t> rp(n + 1, 0); std::vector<int32_t> cl; cl.reserve(nnz);
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t first = cl.size();
+        cl.insert(cl.end(), mask_col + mask_row_ptr[i], mask_col + mask_row_ptr[i + 1]);
+        std::sort(cl.begin() + first, cl.end());
+        cl.erase(std::unique(cl.begin() + first, cl.end()), cl.end());
+        rp[i + 1] = (int64_t)cl.size();
+    }
+    DevBuf<int64_t> drp; DevBuf<int32_t> dcl;                        // uploaded first: a failed copy leaves the handle's mask as it was
+    GEMHIP_CHECK(drp.upload(rp.data(), rp.size()));
+    GEMHIP_CHECK(dcl.upload(cl.data(), cl.size()));
+    h->d_mask_row_ptr = std::move(drp); h->d_mask_col = std::move(dcl);
+    h->mask_row_ptr.swap(rp); h->mask_col.swap(cl);
+    h->has_mask = true;
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_eval_ap_masked(gemhip_eval_t h, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out, int64_t *npos_out)
+{
+    return ap_impl(h, "eval_ap_masked", true, undirected, nsample, nodes, ap_out, npos_out);
+}
+
+extern "C" int gemhip_eval_topk(gemhip_eval_t h, int32_t undirected, int32_t use_mask, int64_t nsample, const int32_t *nodes, int32_t k, int32_t *id_out,
+                                double *score_out, uint8_t *hit_out)
+{
+    GEMHIP_REQUIRE(h && nsample >= 0 && nsample <= INT32_MAX && (nsample == 0 || (nodes && id_out && score_out && hit_out)), "eval_topk: bad arguments");
+    GEMHIP_REQUIRE(k >= 1 && k <= TK_MAXK, "eval_topk: k = %d outside [1,%d]", k, TK_MAXK);
+    GEMHIP_REQUIRE(h->cols_sorted, "eval_topk: the edge lookup needs every CSR row's columns in ascending order");
+    if (nsample == 0) return GEMHIP_OK;
+    const int64_t n = h->n;
+    for (int64_t s = 0; s < nsample; ++s) GEMHIP_REQUIRE(nodes[s] >= 0 && nodes[s] < n, "eval_topk: node %d outside [0,%lld)", nodes[s], (long long)n);
+    const bool masked = use_mask && h->has_mask;
+    const int64_t *dmrp = masked ? h->d_mask_row_ptr.get() : nullptr; const int32_t *dmcol = masked ? h->d_mask_col.get() : nullptr;
+    DevBuf<int32_t> dnodes, did; DevBuf<double> dscore; DevBuf<uint8_t> dhit;
+    const size_t total = (size_t)nsample * (size_t)k;
+    GEMHIP_CHECK(dnodes.upload(nodes, nsample));
+    GEMHIP_CHECK(did.reserve(total)); GEMHIP_CHECK(dscore.reserve(total)); GEMHIP_CHECK(dhit.reserve(total));
+    const int da = h->da, ld = h->ld;
+    const float *dA = h->A, *dB = h->dB();
+    const int nv = (da + WAVE - 1) / WAVE;
+    const size_t lds = (size_t)TK_WAVES * k * (sizeof(double) + sizeof(int));
+#define TK_LAUNCH(NV, KIND) hipLaunchKernelGGL((eval_topk_kernel<NV, KIND>), dim3((unsigned)nsample), dim3(EV_BLOCK), lds, 0, n, da, dA, dB, ld, (int)undirected, \
+                                               dnodes.get(), (int)k, dmrp, dmcol, h->d_row_ptr.get(), h->d_col.get(), did.get(), dscore.get(), dhit.get())
+#define TK_LAUNCH_NV(KIND) do { if (nv <= 1) TK_LAUNCH(1, KIND); else if (nv <= 2) TK_LAUNCH(2, KIND); else if (nv <= 4) TK_LAUNCH(4, KIND); else TK_LAUNCH(8, KIND); } while (0)
+    GEMHIP_CHECK(timed_launch(&h->last_kernel_ms, [&] { if (h->kind == 0) TK_LAUNCH_NV(0); else TK_LAUNCH_NV(1); }));
+#undef TK_LAUNCH_NV
+#undef TK_LAUNCH
+    GEMHIP_CHECK(hipMemcpy(id_out, did, total * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GEMHIP_CHECK(hipMemcpy(score_out, dscore, total * sizeof(double), hipMemcpyDeviceToHost));
+    GEMHIP_CHECK(hipMemcpy(hit_out, dhit, total, hipMemcpyDeviceToHost));
+    return GEMHIP_OK;
+}
+
+extern "C" int gemhip_eval_last_kernel_ms(gemhip_eval_t h, double *ms_out)
+{
+    GEMHIP_REQUIRE(h && ms_out, "eval_last_kernel_ms: bad arguments");
+    *ms_out = h->last_kernel_ms;
     return GEMHIP_OK;
 }
 

@@ -1,2 +1,4 @@
 from gem_amd.evaluation.reconstruction import (evaluateStaticGraphReconstruction, evaluate_reconstruction_gpu, pair_metrics,  # noqa: F401
                                                random_edge_pairs, sampled_ap_gpu)
+from gem_amd.evaluation.link_prediction import (evaluateStaticLinkPrediction, evaluate_link_prediction_gpu, link_prediction_dense,  # noqa: F401
+                                                link_prediction_rows)

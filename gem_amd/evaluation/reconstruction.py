@@ -284,6 +284,40 @@ class _DeviceEvaluator(object):
                                                 _hip.ptr(hit, C.c_uint8)))
         return score, hit
 
+    def set_mask(self, src=None, dst=None):
+        """The train graph of link prediction (gem_amd/evaluation/link_prediction.py): arcs (src -> dst) leave every candidate list of
+        ap_masked and topk.  set_mask() without arguments clears it."""
+        C, _hip = self._C, self._hip
+        if src is None:
+            _hip.check(_hip.lib().gemhip_eval_set_mask(self._h, None, None))
+            return
+        from gem_amd.graph import to_csr
+        row_ptr, col, _ = to_csr(self.n, src, dst, None)
+        _hip.check(_hip.lib().gemhip_eval_set_mask(self._h, _hip.ptr(row_ptr, C.c_int64), _hip.ptr(col, C.c_int32)))
+
+    def ap_masked(self, nodes, is_undirected):
+        """(AP, number of ranked positives) per node, train arcs masked out."""
+        C, _hip = self._C, self._hip
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        out = np.zeros(len(nodes)); npos = np.zeros(len(nodes), dtype=np.int64)
+        _hip.check(_hip.lib().gemhip_eval_ap_masked(self._h, 1 if is_undirected else 0, len(nodes), _hip.ptr(nodes, C.c_int32), _hip.ptr(out, C.c_double),
+                                                    _hip.ptr(npos, C.c_int64)))
+        return out, npos
+
+    def topk(self, nodes, k, is_undirected, use_mask=True):
+        """(id, score, hit), each [len(nodes)][k]: every node's k best candidates in the evaluator's order; id -1 pads a short list."""
+        C, _hip = self._C, self._hip
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        ids = np.zeros((len(nodes), k), dtype=np.int32); score = np.zeros((len(nodes), k)); hit = np.zeros((len(nodes), k), dtype=np.uint8)
+        _hip.check(_hip.lib().gemhip_eval_topk(self._h, 1 if is_undirected else 0, 1 if use_mask else 0, len(nodes), _hip.ptr(nodes, C.c_int32), int(k),
+                                               _hip.ptr(ids, C.c_int32), _hip.ptr(score, C.c_double), _hip.ptr(hit, C.c_uint8)))
+        return ids, score, hit
+
+    def last_kernel_ms(self):
+        ms = self._C.c_double(0.0)
+        self._hip.check(self._hip.lib().gemhip_eval_last_kernel_ms(self._h, self._C.byref(ms)))
+        return ms.value
+
     def last_pairs_ms(self):
         ms = self._C.c_double(0.0)
         self._hip.check(self._hip.lib().gemhip_eval_last_pairs_ms(self._h, self._C.byref(ms)))

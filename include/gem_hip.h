@@ -597,6 +597,27 @@ int gemhip_eval_pairs(gemhip_eval_t h, int64_t npairs, const int32_t *st, const 
                       uint8_t *hit_out);
 /* Device time of the last gemhip_eval_pairs kernel of this handle, milliseconds (HIP events). */
 int gemhip_eval_last_pairs_ms(gemhip_eval_t h, double *ms_out);
+
+/* Link prediction: the handle's CSR is the TEST graph and a second CSR, the TRAIN graph, is a MASK with directed has_edge semantics.
+ * The candidates of node i are the j with j != i, j > i when `undirected`, score(i, j) > 0 (evaluation_util.py:28-35) and (i -> j)
+ * not in the mask, ordered by score descending and node id ascending on ties (Python's stable sorted(..., reverse=True) of metrics.py:12
+ * on the ascending-j list).  The positives of i are its test neighbours that are candidates: a test arc that is also a mask arc is
+ * neither a hit nor a positive.
+ *
+ * gemhip_eval_set_mask copies the mask after validating it on the host as gemhip_eval_create validates its CSR (GEMHIP_E_INVALID, nothing
+ * reaches a kernel); rows are sorted and de-duplicated on the host, the caller need not sort.  mask_row_ptr NULL clears the mask. */
+int gemhip_eval_set_mask(gemhip_eval_t h, const int64_t *mask_row_ptr, const int32_t *mask_col);
+/* ap_out[s] = mean over the positives t of nodes[s] of rank_hit(t) / rank_all(t), both ranks inside the candidate list; 0 without a
+ * positive.  npos_out (may be NULL): the number of positives ranked.  Without a mask, or with an empty one, the bytes of gemhip_eval_ap. */
+int gemhip_eval_ap_masked(gemhip_eval_t h, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out,
+                          int64_t *npos_out);
+/* The first k candidates of every node, [nsample][k]: node id, score, and whether (i -> id) is a test arc; id -1, score 0, hit 0 where a
+ * node has fewer than k candidates.  1 <= k <= 1024.  use_mask 0 ignores the handle's mask.  Exact under the tie rule, identical bytes on
+ * every call, no nsample x n matrix.  Needs the test CSR's columns in ascending order (as gemhip_eval_pairs' edge lookup). */
+int gemhip_eval_topk(gemhip_eval_t h, int32_t undirected, int32_t use_mask, int64_t nsample, const int32_t *nodes, int32_t k,
+                     int32_t *id_out, double *score_out, uint8_t *hit_out);
+/* Device time of the last gemhip_eval_ap, gemhip_eval_ap_masked or gemhip_eval_topk kernel of this handle, milliseconds (HIP events). */
+int gemhip_eval_last_kernel_ms(gemhip_eval_t h, double *ms_out);
 int gemhip_eval_destroy(gemhip_eval_t h);
 
 #ifdef __cplusplus

@@ -35,6 +35,10 @@ int main()
     EXPECT(gemhip_eval_pairs(nullptr, 4, st, ed, s, hit) == GEMHIP_E_INVALID);
     EXPECT(gemhip_eval_ap(nullptr, 1, 4, st, s) == GEMHIP_E_INVALID);
     EXPECT(gemhip_eval_last_pairs_ms(nullptr, s) == GEMHIP_E_INVALID);
+    EXPECT(gemhip_eval_set_mask(nullptr, rp.data(), col.data()) == GEMHIP_E_INVALID);
+    EXPECT(gemhip_eval_ap_masked(nullptr, 1, 4, st, s, nullptr) == GEMHIP_E_INVALID);
+    EXPECT(gemhip_eval_topk(nullptr, 1, 1, 4, st, 1, ed, s, hit) == GEMHIP_E_INVALID);
+    EXPECT(gemhip_eval_last_kernel_ms(nullptr, s) == GEMHIP_E_INVALID);
     EXPECT(gemhip_eval_destroy(nullptr) == GEMHIP_OK);
     const int rc = gemhip_eval_create(n, d, ld, X.data(), nullptr, 0, rp.data(), col.data(), &h);     // well-formed
     if (rc == GEMHIP_OK) {
@@ -45,8 +49,18 @@ int main()
         EXPECT(gemhip_eval_pairs(h, 4, st, bad_st, s, nullptr) == GEMHIP_E_INVALID);
         EXPECT(gemhip_eval_pairs(h, 4, st, ed, s, hit) == GEMHIP_OK);
         EXPECT(hit[0] == 1 && hit[1] == 1 && hit[2] == 0 && hit[3] == 0 && s[2] == 0.0 && s[0] == 0.75);
+        // link prediction: the mask is validated, copied, sorted and de-duplicated on the host
+        std::vector<int64_t> mrp = {0, 3, 3, 3, 4, 4}; std::vector<int32_t> mcol = {4, 2, 4, 0};
+        { auto bad = mcol; bad[1] = 5; EXPECT(gemhip_eval_set_mask(h, mrp.data(), bad.data()) == GEMHIP_E_INVALID); }
+        { auto bad = mrp; bad[2] = 2; EXPECT(gemhip_eval_set_mask(h, bad.data(), mcol.data()) == GEMHIP_E_INVALID); }
+        EXPECT(gemhip_eval_set_mask(h, mrp.data(), mcol.data()) == GEMHIP_OK);
+        int32_t nodes[2] = {0, 3}, ids[4]; double ap[2], sc[4]; int64_t npos[2]; uint8_t th[4];
+        EXPECT(gemhip_eval_ap_masked(h, 0, 2, nodes, ap, npos) == GEMHIP_OK && npos[0] == 1 && npos[1] == 1);     // 0 -> 4 and 3 -> 0 are masked
+        EXPECT(gemhip_eval_topk(h, 0, 1, 2, nodes, 0, ids, sc, th) == GEMHIP_E_INVALID);
+        EXPECT(gemhip_eval_topk(h, 0, 1, 2, nodes, 2, ids, sc, th) == GEMHIP_OK && ids[0] == 1 && ids[1] == 3 && th[0] == 1 && th[1] == 0);
+        EXPECT(gemhip_eval_set_mask(h, nullptr, nullptr) == GEMHIP_OK);
         EXPECT(gemhip_eval_destroy(h) == GEMHIP_OK);
-        std::printf("device present: scored 4 pairs\n");
+        std::printf("device present: scored 4 pairs, masked AP and top-2 of 2 nodes\n");
     } else {
         EXPECT(rc == GEMHIP_E_HIP && h == nullptr);
         std::printf("no device: a well-formed create stopped at its first HIP call (%s)\n", gemhip_last_error());
