@@ -115,6 +115,9 @@ _SIGS = {
     'gemhip_eval_topk': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, i32p, C.c_int32, i32p, f64p, C.POINTER(C.c_uint8)]),
     'gemhip_eval_last_kernel_ms': (C.c_int, [C.c_void_p, f64p]),
     'gemhip_eval_destroy': (C.c_int, [C.c_void_p]),
+    'gemhip_cc_labels': (C.c_int, [C.c_int64, C.c_int64, i32p, i32p, i32p, i32p]),
+    'gemhip_lcc': (C.c_int, [C.c_int64, C.c_int64, i32p, i32p, f32p, i64p, i64p, i32p, i32p, i32p, i32p, f32p, i32p]),
+    'gemhip_cc_last_kernel_ms': (C.c_int, [f64p]),
     'gemhip_n2v_train': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_uint64, C.c_int32, f32p, f64p]),
     'gemhip_n2v_create': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.POINTER(C.c_void_p)]),

@@ -100,11 +100,25 @@ def evaluate_link_prediction_gpu(train_graph, test_graph, graph_embedding, X, no
         return out
 
 
-def evaluateStaticLinkPrediction(digraph, graph_embedding, train_ratio=0.8, nodes=None, sample_ratio_e=None, k=None, is_undirected=True):
+def restrict_to_train_lcc(train, test):
+    """(train', test', new_of_old): the train graph cut down to its largest weakly connected component and renumbered (get_lcc), and the test
+    graph restricted to the arcs between kept nodes, renumbered with the same map, in their original order."""
+    from gem_amd.graph import EdgeListGraph
+    from gem_amd.utils.graph_util import get_lcc
+    train_lcc, new_of_old = get_lcc(train)
+    s, d = new_of_old[test.src], new_of_old[test.dst]
+    keep = (s >= 0) & (d >= 0)
+    return train_lcc, EdgeListGraph(train_lcc.n, s[keep], d[keep], None if test.w is None else test.w[keep]), new_of_old
+
+
+def evaluateStaticLinkPrediction(digraph, graph_embedding, train_ratio=0.8, nodes=None, sample_ratio_e=None, k=None, is_undirected=True, lcc=False):
     """Split `digraph` (split_di_graph_to_train_test: numpy's global stream, so np.random.seed reproduces the split), train
     `graph_embedding` on the train graph, evaluate against the test graph.  Returns (MAP, prec_curv).
-    Every node of `digraph` keeps its id: there is NO relabelling to the largest connected component of the train graph -- X[i] is node i, and
-    nodes the split isolates are embedded and ranked like any other.
+    lcc=False (default): every node of `digraph` keeps its id -- X[i] is node i, and nodes the split isolates are embedded and ranked like any other.
+    lcc=True: what upstream GEM's link-prediction driver does with graph_util.get_lcc after the split -- the train graph is replaced by its largest
+    weakly connected component, renumbered 0..k-1 (gem_amd.utils.graph_util.get_lcc, on the GPU), the test graph is restricted to the kept nodes
+    and renumbered with the same map, `nodes` (old ids) are mapped and the dropped ones left out; X then has one row per KEPT node and every
+    figure below is over the renumbered pair.
       * neither `nodes` nor `sample_ratio_e`, n <= 4096: the dense host path (get_reconstructed_adj of the learned X, link_prediction_dense).
         Above that size one of the two is required.
       * `sample_ratio_e`: evaluate_link_prediction_gpu's pair path.
@@ -112,6 +126,11 @@ def evaluateStaticLinkPrediction(digraph, graph_embedding, train_ratio=0.8, node
     from gem_amd.graph import edge_arrays
     from gem_amd.utils.evaluation_util import split_di_graph_to_train_test
     train, test = split_di_graph_to_train_test(digraph, train_ratio, is_undirected)
+    if lcc:
+        train, test, new_of_old = restrict_to_train_lcc(train, test)
+        if nodes is not None:
+            nodes = new_of_old[np.asarray(nodes, dtype=np.int64)]
+            nodes = nodes[nodes >= 0]
     n = test.n
     if nodes is None and not sample_ratio_e and n > DENSE_MAX_N:
         raise ValueError('evaluateStaticLinkPrediction: %d nodes is above the dense limit of %d: give `nodes` (per-node AP on the GPU) or '

@@ -7,12 +7,34 @@ reference binaries (the real `gf` and `node2vec` executables) through these.
   saveGraphToEdgeListTxtn2v   no header, "%d %d %f"                 (:137-140, input of `node2vec`)
   loadGraphFromEdgeListTxt    "i j [w]" lines -> nx graph           (:143-158)
   loadEmbedding               "n d" header, rows "id v1..vd", row placed at X[id]   (:161-169)
+
+get_lcc (:29-34, the largest weakly connected component, renumbered) is the one function here that computes: on the GPU, gem_amd/csrc/cc.hip.
 """
 import numpy as np
 
 
 def _triples(graph):
     return graph.edges(data='weight', default=1)
+
+
+def get_lcc(di_graph):
+    """(graph, nodeListMap) of gem/utils/graph_util.py:29-34: the largest weakly connected component of `di_graph`, its nodes renumbered
+    0..k-1, and the map old id -> new id.  Computed on the GPU (gem_amd.graph.lcc_arrays; GemHipError without a device).
+      * nx.DiGraph in: a new nx.DiGraph (nodes 0..k-1, the kept arcs in their original order with their weights) and a dict {old: new} of the
+        kept nodes, as the reference returns them;
+      * EdgeListGraph in: an EdgeListGraph and the int32 array new_of_old over ALL old ids, -1 where the node was dropped.
+    New ids ascend with old ids; the reference numbers in node-insertion order and breaks a tie between largest components by it, which is the
+    same whenever nodes were inserted in id order (gem_amd.graph.largest_component)."""
+    from gem_amd.graph import EdgeListGraph, edge_arrays, lcc_arrays
+    n, src, dst, w, _ = edge_arrays(di_graph)
+    _, old_of_new, new_of_old, s, d, ww = lcc_arrays(n, src, dst, w)
+    if isinstance(di_graph, EdgeListGraph):
+        return EdgeListGraph(len(old_of_new), s, d, ww), new_of_old
+    import networkx as nx
+    G = nx.DiGraph()
+    G.add_nodes_from(range(len(old_of_new)))
+    G.add_weighted_edges_from(zip(s.tolist(), d.tolist(), ww.astype(np.float64).tolist()))
+    return G, dict(zip(old_of_new.tolist(), range(len(old_of_new))))
 
 
 def saveGraphToEdgeListTxt(graph, file_name):

@@ -51,7 +51,8 @@ int gemhip_synchronize(void *stream);
 /* Where the wall time of the LAST one-shot call on this thread went (gemhip_gf_train, gemhip_n2v_train, gemhip_hope: the drop-ins
  * for gf.py:55-72, node2vec.py:35-48 and hope.py:28-36, whose callers time `learn_embedding` as a whole -- SURVEY 8d "API wall"):
  * out[8] = {total_seconds, host_prepare_seconds (CSR sort, alias / unigram tables, plans), h2d_seconds, kernel_seconds (HIP events),
- * d2h_seconds, 0, 0, 0}. */
+ * d2h_seconds, 0, 0, 0}.  gemhip_cc_labels and gemhip_lcc (the drop-in for graph_util.py:29-34, get_lcc) fill it too: host_prepare is their
+ * validation of the arc list, kernel_seconds the sum gemhip_cc_last_kernel_ms splits. */
 int gemhip_last_call_phases(double *out);
 
 /* ------------------------------------------------- Graph Factorization (GF)
@@ -619,6 +620,32 @@ int gemhip_eval_topk(gemhip_eval_t h, int32_t undirected, int32_t use_mask, int6
 /* Device time of the last gemhip_eval_ap, gemhip_eval_ap_masked or gemhip_eval_topk kernel of this handle, milliseconds (HIP events). */
 int gemhip_eval_last_kernel_ms(gemhip_eval_t h, double *ms_out);
 int gemhip_eval_destroy(gemhip_eval_t h);
+
+/* ------------------------------------------- connected components, largest component
+ * Replaces: gem/utils/graph_util.py:29-34 (get_lcc: the largest weakly connected component of a graph, its nodes renumbered 0..k-1), which
+ * upstream's link-prediction driver applies to the train graph of a split.  (That function calls nx.weakly_connected_component_subgraphs, which current networkx no longer has.)
+ *
+ * The graph is the arc list of the GF entry points: m arcs (src, dst[, w]) in any order.  Direction is ignored (WEAK connectivity); self-loops
+ * and duplicate arcs are legal; m = 0 is legal (every node its own component).  1 <= n < 2^31 and m < 2^31, otherwise GEMHIP_E_UNSUPPORTED
+ * (n < 1: GEMHIP_E_INVALID).  Validated on the host before any device call, like gemhip_gf_objective: a NULL pointer, or an arc outside [0, n)
+ * (named as gemhip_gf_train names it: "lcc: edge 1 = (1,5) outside [0,5)"), is GEMHIP_E_INVALID.
+ *
+ * Device: lock-free union-find, one thread per arc, then one kernel per phase (DESIGN.md "Connected components"); no thread waits for another.
+ * Every result is exact and identical on every run.
+ *
+ * labels_out[v] = the smallest node id of v's component; *n_components_out = the number of components. */
+int gemhip_cc_labels(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, int32_t *labels_out, int32_t *n_components_out);
+/* The largest component; of several largest ones, the one with the smallest label (= holding the smallest node id).
+ * *n_out nodes and *m_out arcs are kept.  new_of_old[n]: the new id of every node, ascending with the old id, -1 where the node is dropped;
+ * old_of_new[0 .. *n_out): its inverse.  src_out / dst_out / w_out [0 .. *m_out): the arcs whose source is kept (their target then is too), in
+ * their original order, both ends renumbered, weights copied bit for bit.  old_of_new needs room for n entries, src_out / dst_out / w_out for m;
+ * entries past *n_out / *m_out are not written.  w and w_out are both given or both NULL; src_out / dst_out may be NULL when m = 0. */
+int gemhip_lcc(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, const float *w /* or NULL */, int64_t *n_out, int64_t *m_out,
+               int32_t *old_of_new, int32_t *new_of_old, int32_t *src_out, int32_t *dst_out, float *w_out /* or NULL */,
+               int32_t *n_components_out);
+/* Device time of the kernels of the last gemhip_cc_labels / gemhip_lcc call on this thread, milliseconds (HIP events): out[8] = {init, union,
+ * flatten (labels), component sizes, winner, node compaction, arc compaction, 0}; the last two are 0 after gemhip_cc_labels. */
+int gemhip_cc_last_kernel_ms(double *out);
 
 #ifdef __cplusplus
 }
