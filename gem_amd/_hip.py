@@ -118,6 +118,17 @@ _SIGS = {
     'gemhip_cc_labels': (C.c_int, [C.c_int64, C.c_int64, i32p, i32p, i32p, i32p]),
     'gemhip_lcc': (C.c_int, [C.c_int64, C.c_int64, i32p, i32p, f32p, i64p, i64p, i32p, i32p, i32p, i32p, f32p, i32p]),
     'gemhip_cc_last_kernel_ms': (C.c_int, [f64p]),
+    'gemhip_tsne_create': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, C.c_double, C.POINTER(C.c_void_p)]),
+    'gemhip_tsne_set_embedding': (C.c_int, [C.c_void_p, f32p]),
+    'gemhip_tsne_run': (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, f64p, f64p]),
+    'gemhip_tsne_get_embedding': (C.c_int, [C.c_void_p, f32p]),
+    'gemhip_tsne_last_ms': (C.c_int, [C.c_void_p, f64p]),
+    'gemhip_tsne_info': (C.c_int, [C.c_void_p, i64p]),
+    'gemhip_tsne_destroy': (C.c_int, [C.c_void_p]),
+    'gemhip_tsne_knn': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, C.c_int32, i32p, f32p]),
+    'gemhip_tsne_affinities': (C.c_int, [C.c_int64, C.c_int32, f32p, C.c_double, f32p]),
+    'gemhip_tsne_set_affinities': (C.c_int, [C.c_void_p, i32p, f32p]),
+    'gemhip_tsne_gradient': (C.c_int, [C.c_void_p, C.c_double, f32p, f64p, f64p]),
     'gemhip_n2v_train': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_uint64, C.c_int32, f32p, f64p]),
     'gemhip_n2v_create': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.POINTER(C.c_void_p)]),

@@ -647,6 +647,44 @@ int gemhip_lcc(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, con
  * flatten (labels), component sizes, winner, node compaction, arc compaction, 0}; the last two are 0 after gemhip_cc_labels. */
 int gemhip_cc_last_kernel_ms(double *out);
 
+/* ------------------------------------------- t-SNE to two dimensions (embedding plots)
+ * Replaces: gem/evaluation/visualize_embedding.py:9-12, where an embedding with d > 2 goes through sklearn.manifold.TSNE(n_components=2)
+ * before it is plotted.  The scheme: k nearest neighbours with k = min(n - 1, floor(3 * perplexity) + 1), sklearn's binary
+ * search of the conditional affinities p_{j|i} over them, P = (p_{j|i} + p_{i|j}) / 2n held as the kNN lists and their transpose (never merged,
+ * never n x n), the repulsive term summed EXACTLY over all pairs (no tree), sklearn's gradient descent with gains and momentum.
+ * No floating-point atomics, every reduction in a fixed order: identical bits on every run.
+ *
+ * gemhip_tsne_create: X_host [n][ld] float32, 1 <= d <= ld.  5 <= perplexity <= 100 and perplexity < n, every value finite and at most 1e15 in
+ * magnitude, n * k < 2^31: otherwise GEMHIP_E_INVALID (GEMHIP_E_UNSUPPORTED for the last), checked on the host before any device call.
+ * Runs the kNN search, the affinities and the transpose.  The embedding Y is [n][2] float32 and must be set before the first run. */
+typedef struct gemhip_tsne *gemhip_tsne_t;
+int gemhip_tsne_create(int64_t n, int32_t d, int32_t ld, const float *X_host, double perplexity, gemhip_tsne_t *out);
+/* Sets Y and resets the optimiser's state (update = 0, gains = 1). */
+int gemhip_tsne_set_embedding(gemhip_tsne_t h, const float *Y_host);
+/* n_iter steps of sklearn's _gradient_descent at fixed arguments: grad = 4 (exaggeration * attr - rep / Z); gains += 0.2 where update * grad < 0,
+ * otherwise *= 0.8, at least 0.01; update = momentum * update - lr * gains * grad; Y += update.  The optimiser's state carries over from call to
+ * call.  *kl_out (may be NULL): KL(P || Q) of the UNEXAGGERATED P at the Y the last step's gradient was taken at; *grad_norm_out (may be NULL):
+ * the 2-norm of that step's gains * grad, the quantity sklearn's min_grad_norm rule looks at.  n_iter >= 1. */
+int gemhip_tsne_run(gemhip_tsne_t h, int32_t n_iter, double exaggeration, double momentum, double lr, double *kl_out, double *grad_norm_out);
+int gemhip_tsne_get_embedding(gemhip_tsne_t h, float *Y_out);
+/* Device time, milliseconds (HIP events): out[4] = {kNN search, affinities, transpose, the last gemhip_tsne_run}. */
+int gemhip_tsne_last_ms(gemhip_tsne_t h, double *out);
+/* out[4] = {n, d, k, number of j-slices of the repulsion grid}. */
+int gemhip_tsne_info(gemhip_tsne_t h, int64_t *out);
+int gemhip_tsne_destroy(gemhip_tsne_t h);
+/* Stages on their own (tests).
+ * gemhip_tsne_knn: for every row the k nearest OTHER rows, 1 <= k <= min(n - 1, 301): id_out / dist_out [n][k], ascending by (distance, id),
+ * distance = sum_c (x_ic - x_jc)^2 in fp32.  Candidates are chosen by ||a||^2 + ||b||^2 - 2 a.b of the mean-centred rows (fp32 matrix units).
+ * gemhip_tsne_affinities: dist [n][k] float32 -> p_out [n][k] float32, sklearn's _binary_search_perplexity (fp64, at most 100 steps, 1e-5 on the
+ * entropy), 1 <= k <= 320.
+ * gemhip_tsne_set_affinities: replaces the handle's kNN lists and conditional P by the caller's, [n][k] each with the handle's k; ids are
+ * checked against [0, n) and the row itself on the host.
+ * gemhip_tsne_gradient: the gradient at the handle's Y, [n][2] float32, the KL of the unexaggerated P and Z = sum_{i != j} 1 / (1 + |y_i - y_j|^2). */
+int gemhip_tsne_knn(int64_t n, int32_t d, int32_t ld, const float *X_host, int32_t k, int32_t *id_out, float *dist_out);
+int gemhip_tsne_affinities(int64_t n, int32_t k, const float *dist, double perplexity, float *p_out);
+int gemhip_tsne_set_affinities(gemhip_tsne_t h, const int32_t *id, const float *p);
+int gemhip_tsne_gradient(gemhip_tsne_t h, double exaggeration, float *grad_out, double *kl_out, double *z_out);
+
 #ifdef __cplusplus
 }
 #endif
