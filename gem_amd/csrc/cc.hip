@@ -275,17 +275,16 @@ int grid_for(int64_t count)
 enum { K_INIT = 0, K_UNION, K_FLATTEN, K_SIZES, K_WINNER, K_NODES, K_ARCS, K_COUNT };
 double *kernel_ms() { static thread_local double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; return ms; }
 
-struct Events {                                         // K_COUNT + 1 marks on the null stream, owned
-    hipEvent_t ev[K_COUNT + 1] = {};
+struct Events {                                         // K_COUNT + 1 marks on the null stream, taken in order
+    EventMarks<K_COUNT + 1> ev;
     int marked = 0;
-    ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    hipError_t create() { for (hipEvent_t &e : ev) { const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; } return hipSuccess; }
-    hipError_t mark() { return hipEventRecord(ev[marked++], 0); }
-    hipError_t collect()                                // after the stream has drained: ms between consecutive marks
+    hipError_t create() { return ev.create(); }
+    hipError_t mark() { return ev.mark(marked++); }
+    hipError_t collect()                                // ms between consecutive marks
     {
         for (int k = 0; k + 1 < marked; ++k) {
-            float ms = 0.f;
-            const hipError_t r = hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
+            double ms = 0.0;
+            const hipError_t r = ev.ms(k, k + 1, &ms);
             if (r != hipSuccess) return r;
             kernel_ms()[k] = ms;
             phase_acc()[PH_KERNELS] += ms * 1e-3;

@@ -91,6 +91,37 @@ public:
 template <typename T> using DevBuf = Buf<T, false>;
 template <typename T> using PinnedBuf = Buf<T, true>;
 
+// ---------------------------------------------------------------- owned timing events
+// The one owner of the library's timing events: N marks, move-only, destroyed in the destructor.  (Ordering events made with
+// hipEventDisableTiming -- GF's hub fork/join, HOPE's CoefSlot::done -- and HOPE's growing SpMM pool are not marks and stay where they are.)
+template <int N>
+struct EventMarks {
+    hipEvent_t ev[N] = {};
+    EventMarks() = default;
+    EventMarks(const EventMarks &) = delete;
+    EventMarks &operator=(const EventMarks &) = delete;
+    EventMarks(EventMarks &&o) noexcept { take(o); }
+    EventMarks &operator=(EventMarks &&o) noexcept { if (this != &o) { destroy(); take(o); } return *this; }
+    ~EventMarks() { destroy(); }
+    hipError_t create()                                             // idempotent: makes the events that are not there yet
+    {
+        for (hipEvent_t &e : ev) if (!e) { const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) { e = nullptr; return r; } }
+        return hipSuccess;
+    }
+    hipError_t mark(int k, hipStream_t s = 0) { return hipEventRecord(ev[k], s); }
+    hipError_t ms(int from, int to, double *out)                    // waits for mark `to`; *out is written on success only
+    {
+        hipError_t e = hipEventSynchronize(ev[to]);
+        float f = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&f, ev[from], ev[to]);
+        if (e == hipSuccess) *out = f;
+        return e;
+    }
+private:
+    void destroy() { for (hipEvent_t &e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } }
+    void take(EventMarks &o) { for (int k = 0; k < N; ++k) { ev[k] = o.ev[k]; o.ev[k] = nullptr; } }
+};
+
 constexpr int WAVE = 64;          // CDNA wavefront
 constexpr int NUM_XCD = 8;        // MI355X: 8 XCDs, block b lands on XCD b % 8
 
@@ -111,6 +142,14 @@ __device__ __forceinline__ float wave_sum(float v)
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 32));
     const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 48));
     return (r0 + r1) + (r2 + r3);
+}
+
+// Wave-wide fp64 sum by a butterfly: the same bits in every lane.
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
 }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }

@@ -26,9 +26,13 @@
 // and, with a second graph as a mask (gemhip_eval_set_mask: the TRAIN graph of a link-prediction split, the handle's CSR being the TEST graph):
 //   gemhip_eval_ap_masked  the same AP with the training arcs taken out of every candidate list;
 //   gemhip_eval_topk       every sampled node's k best candidates, in the evaluator's order.
+// This file holds the kernels, the handle and the entry points; what the host computes around the launches (the CSR check, the mask's normal form,
+// the chunks, AP from the counts) is eval_host.hip, which needs no device.
 #include "common.hpp"
+#include "eval_host.hpp"
 #include <algorithm>
 #include <climits>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -37,15 +41,7 @@ using namespace gemhip;
 namespace {
 
 constexpr int EV_BLOCK = 256;
-constexpr int EV_MAXNB = 512;                 // true neighbours per sampled node handled in registers
-constexpr int EV_NREG = EV_MAXNB / WAVE;
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+constexpr int EV_NREG = EV_MAXNB / WAVE;       // EV_MAXNB (eval_host.hpp) true neighbours per chunk, held in registers
 
 template <int KIND>
 __device__ __forceinline__ double finish_score(double sum)      // sum: the fp64 dot (kind 0) or the fp64 squared distance (kind 1)
@@ -61,63 +57,6 @@ __device__ __forceinline__ double term(float a, float b)
     if (KIND == 0) return (double)a * (double)b;
     const double t = (double)a - (double)b;
     return t * t;
-}
-
-template <int NV, int KIND>     // lane l holds columns (c*64 + l), c < NV  (da <= 64*NV)
-__global__ __launch_bounds__(EV_BLOCK) void eval_ap_kernel(int64_t n, int da, const float *__restrict__ A, const float *__restrict__ B, int ldb,
-                                                           int undirected, const int32_t *__restrict__ chunk_node, const int64_t *__restrict__ chunk_off,
-                                                           const int32_t *__restrict__ chunk_cnt, const int32_t *__restrict__ nb,
-                                                           double *__restrict__ s_out, int32_t *__restrict__ cnt_out)
-{
-    // One workgroup per (sampled node, chunk of <= EV_MAXNB of its true neighbours): hubs of a power-law graph take several chunks.
-    __shared__ double s_nb[EV_MAXNB];
-    __shared__ int t_nb[EV_MAXNB];
-    __shared__ int cnt_nb[EV_MAXNB];
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const int i = chunk_node[blockIdx.x];
-    const int64_t off = chunk_off[blockIdx.x];
-    const int nnb = chunk_cnt[blockIdx.x];
-    for (int k = threadIdx.x; k < EV_MAXNB; k += EV_BLOCK) { cnt_nb[k] = 0; t_nb[k] = k < nnb ? nb[off + k] : -1; }
-    __syncthreads();
-    float a[NV];
-#pragma unroll
-    for (int c = 0; c < NV; ++c) { const int cc = c * WAVE + lane; a[c] = cc < da ? A[(int64_t)i * ldb + cc] : 0.f; }
-    auto score = [&](int64_t j) -> double {
-        double part = 0.0;
-        const float *bj = B + j * ldb;
-#pragma unroll
-        for (int c = 0; c < NV; ++c) { const int cc = c * WAVE + lane; if (cc < da) part += term<KIND>(a[c], bj[cc]); }
-        return finish_score<KIND>(wave_sum_f64(part));
-    };
-    for (int k = wave; k < nnb; k += EV_BLOCK / WAVE) {
-        const double s = score(t_nb[k]);
-        if (lane == 0) s_nb[k] = s;
-    }
-    __syncthreads();
-    double my_s[EV_NREG]; int my_t[EV_NREG]; int my_c[EV_NREG];
-#pragma unroll
-    for (int r = 0; r < EV_NREG; ++r) {
-        const int k = r * WAVE + lane;
-        my_s[r] = k < nnb ? s_nb[k] : 0.0; my_t[r] = k < nnb ? t_nb[k] : -1; my_c[r] = 0;
-    }
-    // ---- stream the candidates (j != i, and j > i when undirected: evaluation_util.py:28-35)
-    const int64_t lo = undirected ? (int64_t)i + 1 : 0;
-    const int nreg_used = (nnb + WAVE - 1) / WAVE;
-    for (int64_t j = lo + wave; j < n; j += EV_BLOCK / WAVE) {
-        if (j == i) continue;
-        const double s = score(j);
-        if (!(s > 0.0)) continue;                                  // evaluation_util.py:34  adj[i, j] > threshold (0.0)
-#pragma unroll
-        for (int r = 0; r < EV_NREG; ++r)
-            if (r < nreg_used) my_c[r] += (s > my_s[r] || (s == my_s[r] && j < my_t[r])) ? 1 : 0;
-    }
-#pragma unroll
-    for (int r = 0; r < EV_NREG; ++r) {
-        const int k = r * WAVE + lane;
-        if (k < nnb && my_c[r]) atomicAdd(&cnt_nb[k], my_c[r]);
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < nnb; k += EV_BLOCK) { s_out[off + k] = s_nb[k]; cnt_out[off + k] = cnt_nb[k]; }
 }
 
 // ---- link prediction: the handle's CSR is the TEST graph, a second CSR (the TRAIN graph, rows sorted and de-duplicated by
@@ -142,8 +81,10 @@ struct MaskWalk {
     }
 };
 
-// A_i in registers and the fp64 score of a row of B, in eval_ap_kernel's own arithmetic (same lane-to-column map, same order of the sums).
-template <int NV, int KIND>
+struct NoMask { __device__ __forceinline__ bool masked(int64_t) const { return false; } };      // what an unmasked stream asks instead: nothing, no state
+
+// A_i in registers and the fp64 score of a row of B: the one row score of the AP and top-k kernels.
+template <int NV, int KIND>     // lane l holds columns (c*64 + l), c < NV  (da <= 64*NV)
 struct RowScore {
     float a[NV]; const float *B; int ldb, da, lane;
     __device__ __forceinline__ RowScore(const float *__restrict__ A, const float *__restrict__ B_, int ldb_, int da_, int i) : B(B_), ldb(ldb_), da(da_), lane(lane_id())
@@ -161,14 +102,15 @@ struct RowScore {
     }
 };
 
-// eval_ap_kernel with the mask applied in the stream.  The chunks hold the POSITIVES of i (its test neighbours that are not masked; the host
-// removes the masked ones), and rank_all counts unmasked candidates only.  mask_row_ptr == nullptr: no mask, the counts of eval_ap_kernel.
-template <int NV, int KIND>
-__global__ __launch_bounds__(EV_BLOCK) void eval_ap_masked_kernel(int64_t n, int da, const float *__restrict__ A, const float *__restrict__ B, int ldb,
-                                                                  int undirected, const int32_t *__restrict__ chunk_node, const int64_t *__restrict__ chunk_off,
-                                                                  const int32_t *__restrict__ chunk_cnt, const int32_t *__restrict__ nb,
-                                                                  const int64_t *__restrict__ mask_row_ptr, const int32_t *__restrict__ mask_col,
-                                                                  double *__restrict__ s_out, int32_t *__restrict__ cnt_out)
+// The AP kernel.  One workgroup per (sampled node, chunk of <= EV_MAXNB of its positives): hubs of a power-law graph take several chunks.
+// MASKED: the mask is applied in the stream -- the chunks hold the POSITIVES of i (its test neighbours that are not masked; the host removes the
+// masked ones), and rank_all counts unmasked candidates only.  Without it no MaskWalk exists (NoMask stands in) and the mask arguments are not read.
+template <int NV, int KIND, bool MASKED>
+__global__ __launch_bounds__(EV_BLOCK) void eval_ap_kernel(int64_t n, int da, const float *__restrict__ A, const float *__restrict__ B, int ldb,
+                                                           int undirected, const int32_t *__restrict__ chunk_node, const int64_t *__restrict__ chunk_off,
+                                                           const int32_t *__restrict__ chunk_cnt, const int32_t *__restrict__ nb,
+                                                           const int64_t *__restrict__ mask_row_ptr, const int32_t *__restrict__ mask_col,
+                                                           double *__restrict__ s_out, int32_t *__restrict__ cnt_out)
 {
     __shared__ double s_nb[EV_MAXNB];
     __shared__ int t_nb[EV_MAXNB];
@@ -191,14 +133,15 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_ap_masked_kernel(int64_t n, int
         const int k = r * WAVE + lane;
         my_s[r] = k < nnb ? s_nb[k] : 0.0; my_t[r] = k < nnb ? t_nb[k] : -1; my_c[r] = 0;
     }
+    // ---- stream the candidates (j != i, and j > i when undirected: evaluation_util.py:28-35; not a mask arc)
     const int64_t lo = undirected ? (int64_t)i + 1 : 0;
     const int nreg_used = (nnb + WAVE - 1) / WAVE;
-    MaskWalk mask;
-    mask.open(mask_row_ptr, mask_col, i, lo);
+    std::conditional_t<MASKED, MaskWalk, NoMask> mask;
+    if constexpr (MASKED) mask.open(mask_row_ptr, mask_col, i, lo);
     for (int64_t j = lo + wave; j < n; j += EV_BLOCK / WAVE) {
         if (j == i || mask.masked(j)) continue;
         const double s = score(j);
-        if (!(s > 0.0)) continue;
+        if (!(s > 0.0)) continue;                                  // evaluation_util.py:34  adj[i, j] > threshold (0.0)
 #pragma unroll
         for (int r = 0; r < EV_NREG; ++r)
             if (r < nreg_used) my_c[r] += (s > my_s[r] || (s == my_s[r] && j < my_t[r])) ? 1 : 0;
@@ -210,6 +153,15 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_ap_masked_kernel(int64_t n, int
     }
     __syncthreads();
     for (int k = threadIdx.x; k < nnb; k += EV_BLOCK) { s_out[off + k] = s_nb[k]; cnt_out[off + k] = cnt_nb[k]; }
+}
+
+// Is (i -> j) an arc of the CSR: bisects row i, whose columns are ascending.
+__device__ __forceinline__ bool csr_has_arc(const int64_t *row_ptr, const int32_t *col, int i, int j)
+{
+    int64_t hi = row_ptr[i + 1], lo = row_ptr[i];
+    const int64_t end = hi;
+    while (lo < hi) { const int64_t mid = lo + ((hi - lo) >> 1); if (col[mid] < j) lo = mid + 1; else hi = mid; }
+    return lo < end && col[lo] == j;
 }
 
 // ---- per-node top-k: one workgroup per sampled node, the same row stream and mask walk.  Every wavefront keeps the k best of the rows IT
@@ -295,10 +247,8 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_topk_kernel(int64_t n, int da, 
             for (int q = 0; q < c2; ++q) rank += ranks_before(s2[q], id2[q], s, id) ? 1 : 0;
         }
         if (rank >= k) continue;
-        int64_t lo_e = row_ptr[i], hi_e = row_ptr[i + 1];          // is (i -> id) a test arc: eval_pairs_kernel's search, columns sorted
-        const int64_t end_e = hi_e;
-        while (lo_e < hi_e) { const int64_t mid = lo_e + ((hi_e - lo_e) >> 1); if (col[mid] < id) lo_e = mid + 1; else hi_e = mid; }
-        id_out[out + rank] = id; score_out[out + rank] = s; hit_out[out + rank] = (lo_e < end_e && col[lo_e] == id) ? 1 : 0;
+        const bool hit = csr_has_arc(row_ptr, col, i, id);         // is (i -> id) a test arc
+        id_out[out + rank] = id; score_out[out + rank] = s; hit_out[out + rank] = hit ? 1 : 0;
     }
     for (int r = (total < k ? total : k) + threadIdx.x; r < k; r += EV_BLOCK) { id_out[out + r] = -1; score_out[out + r] = 0.0; hit_out[out + r] = 0; }
 }
@@ -357,13 +307,48 @@ __global__ __launch_bounds__(EP_BLOCK) void eval_pairs_kernel(int da, int ld, co
         for (int o = EP_GROUP / 2; o >= 1; o >>= 1) part += __shfl_xor(part, o);       // partners stay inside the group, which is all active or all idle
         if (sub == 0) {
             score_out[p] = i == j ? 0.0 : finish_score<KIND>(part);                   // zero diagonal of get_reconstructed_adj
-            if (hit_out) {                                                             // true_digraph.has_edge(st, ed): directed, columns sorted
-                int64_t lo = row_ptr[i], hi = row_ptr[i + 1];
-                const int64_t end = hi;
-                while (lo < hi) { const int64_t mid = lo + ((hi - lo) >> 1); if (col[mid] < j) lo = mid + 1; else hi = mid; }
-                hit_out[p] = (lo < end && col[lo] == j) ? 1 : 0;
-            }
+            if (hit_out) hit_out[p] = csr_has_arc(row_ptr, col, i, j) ? 1 : 0;        // true_digraph.has_edge(st, ed): directed
         }
+    }
+}
+
+// ---- host side
+// Runs `launch` between two marks on the null stream, waits for it and stores the device time in *ms.
+template <typename Launch>
+hipError_t timed_launch(double *ms, Launch launch)
+{
+    EventMarks<2> t;
+    hipError_t e = t.create();
+    if (e != hipSuccess) return e;
+    (void)t.mark(0);
+    launch();
+    e = hipGetLastError();
+    (void)t.mark(1);
+    return e != hipSuccess ? e : t.ms(0, 1, ms);
+}
+
+// The one map from a handle's (kind, da) to the kernels' compile-time <NV, KIND>: f(integral_constant NV, integral_constant KIND).
+template <typename F>
+void dispatch_width(int kind, int da, F f)
+{
+    auto with_nv = [&](auto NV) {
+        if (kind == 0) f(NV, std::integral_constant<int, 0>{}); else f(NV, std::integral_constant<int, 1>{});
+    };
+    const int nv = (da + WAVE - 1) / WAVE;
+    if (nv <= 1) with_nv(std::integral_constant<int, 1>{});
+    else if (nv <= 2) with_nv(std::integral_constant<int, 2>{});
+    else if (nv <= 4) with_nv(std::integral_constant<int, 4>{});
+    else with_nv(std::integral_constant<int, 8>{});
+}
+
+// The refusal of a CSR that check_eval_csr did not pass, in the words of `who`.
+int refuse_csr(const char *who, const EvalCsrError &err, int64_t n, const int64_t *row_ptr)
+{
+    switch (err.kind) {
+    case EvalCsrError::ROW_PTR_FIRST: return fail(GEMHIP_E_INVALID, "%s: row_ptr[0] is %lld, not 0", who, (long long)row_ptr[0]);
+    case EvalCsrError::ROW_PTR_DECREASES: return fail(GEMHIP_E_INVALID, "%s: row_ptr decreases at row %lld", who, (long long)err.index);
+    case EvalCsrError::COL_NULL: return fail(GEMHIP_E_INVALID, "%s: col is null", who);
+    default: return fail(GEMHIP_E_INVALID, "%s: column %d outside [0,%lld)", who, err.column, (long long)n);
     }
 }
 
@@ -375,7 +360,7 @@ struct gemhip_eval {
     DevBuf<float> A, B; DevBuf<int64_t> d_row_ptr; DevBuf<int32_t> d_col;
     DevBuf<int32_t> d_st, d_ed; DevBuf<double> d_score; DevBuf<uint8_t> d_hit;     // pair scratch, grow-only
     bool has_mask = false;                                           // link prediction: the train graph, rows sorted and de-duplicated
-    std::vector<int64_t> mask_row_ptr; std::vector<int32_t> mask_col;
+    EvalMask mask;
     DevBuf<int64_t> d_mask_row_ptr; DevBuf<int32_t> d_mask_col;
     double last_pairs_ms = 0.0, last_kernel_ms = 0.0;
     const float *dB() const { return B ? B.get() : A.get(); }
@@ -389,16 +374,9 @@ extern "C" int gemhip_eval_create(int64_t n, int32_t da, int32_t ld, const float
     GEMHIP_REQUIRE(n >= 1 && n <= INT32_MAX && da >= 1 && da <= 512 && ld >= da && A_host && row_ptr, "eval_create: bad arguments (1 <= da <= 512, ld >= da, n < 2^31)");
     GEMHIP_REQUIRE(kind == 0 || kind == 1, "eval_create: kind %d is neither 0 (inner product) nor 1 (exp of minus squared distance)", kind);
     GEMHIP_REQUIRE(kind == 0 || !B_host || B_host == A_host, "eval_create: kind 1 scores one embedding against itself (B must be NULL)");
-    GEMHIP_REQUIRE(row_ptr[0] == 0, "eval_create: row_ptr[0] is %lld, not 0", (long long)row_ptr[0]);
-    for (int64_t i = 0; i < n; ++i) GEMHIP_REQUIRE(row_ptr[i + 1] >= row_ptr[i], "eval_create: row_ptr decreases at row %lld", (long long)i);
-    const int64_t nnz = row_ptr[n];
-    GEMHIP_REQUIRE(nnz == 0 || col, "eval_create: col is null");
     bool sorted = true;
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
-            GEMHIP_REQUIRE(col[e] >= 0 && col[e] < n, "eval_create: column %d outside [0,%lld)", col[e], (long long)n);
-            if (e > row_ptr[i] && col[e] < col[e - 1]) sorted = false;
-        }
+    if (const EvalCsrError err = check_eval_csr(n, row_ptr, col, &sorted)) return refuse_csr("eval_create", err, n, row_ptr);
+    const int64_t nnz = row_ptr[n];
     gemhip_eval *h = new gemhip_eval;
     h->n = n; h->nnz = nnz; h->da = da; h->ld = ld; h->kind = kind; h->cols_sorted = sorted;
     h->row_ptr.assign(row_ptr, row_ptr + n + 1);
@@ -421,96 +399,38 @@ extern "C" int gemhip_eval_destroy(gemhip_eval_t h)
 
 namespace {
 
-// Runs `launch` between two HIP events on the null stream, waits for it and stores the device time in *ms.
-template <typename Launch>
-hipError_t timed_launch(double *ms, Launch launch)
-{
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e != hipSuccess) return e;
-    e = hipEventCreate(&e1);
-    if (e != hipSuccess) { (void)hipEventDestroy(e0); return e; }
-    (void)hipEventRecord(e0, 0);
-    launch();
-    e = hipGetLastError();
-    (void)hipEventRecord(e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    float t = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (e == hipSuccess) *ms = t;
-    return e;
-}
-
-// gemhip_eval_ap (masked = false: eval_ap_kernel, the handle's mask is ignored) and gemhip_eval_ap_masked (eval_ap_masked_kernel).
+// gemhip_eval_ap (masked = false: the handle's mask is ignored) and gemhip_eval_ap_masked: validate, ap_chunks, upload, launch, download, ap_from_counts.
 int ap_impl(gemhip_eval_t h, const char *who, bool masked, int32_t undirected, int64_t nsample, const int32_t *nodes, double *ap_out, int64_t *npos_out)
 {
     GEMHIP_REQUIRE(h && nsample >= 0 && (nsample == 0 || (nodes && ap_out)), "%s: bad arguments", who);
     if (nsample == 0) return GEMHIP_OK;
     const int64_t n = h->n;
-    const int64_t *row_ptr = h->row_ptr.data(); const int32_t *col = h->col.data();
     for (int64_t k = 0; k < nsample; ++k) GEMHIP_REQUIRE(nodes[k] >= 0 && nodes[k] < n, "%s: node %d outside [0,%lld)", who, nodes[k], (long long)n);
     const bool use_mask = masked && h->has_mask;
-    // ---- candidate true neighbours of every sampled node (j != i, j > i when undirected, not a mask arc, each once), cut into chunks
-    std::vector<int32_t> nb, chunk_node, chunk_cnt; std::vector<int64_t> chunk_off, node_off(nsample + 1, 0);
-    std::vector<int32_t> tmp;
-    for (int64_t k = 0; k < nsample; ++k) {
-        const int i = nodes[k];
-        tmp.clear();
-        const int32_t *mb = use_mask ? h->mask_col.data() + h->mask_row_ptr[i] : nullptr, *me = use_mask ? h->mask_col.data() + h->mask_row_ptr[i + 1] : nullptr;
-        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
-            const int t = col[e];
-            if (t == i || (undirected && t < i)) continue;
-            if (use_mask && std::binary_search(mb, me, t)) continue;
-            tmp.push_back(t);
-        }
-        std::sort(tmp.begin(), tmp.end());
-        tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-        for (size_t o = 0; o < tmp.size(); o += EV_MAXNB) {
-            chunk_node.push_back(i); chunk_off.push_back((int64_t)nb.size() + (int64_t)o);
-            chunk_cnt.push_back((int32_t)std::min<size_t>(EV_MAXNB, tmp.size() - o));
-        }
-        nb.insert(nb.end(), tmp.begin(), tmp.end());
-        node_off[k + 1] = (int64_t)nb.size();
-    }
-    const int64_t nchunk = (int64_t)chunk_node.size(), total = (int64_t)nb.size();
+    const ApChunks c = ap_chunks(h->row_ptr.data(), h->col.data(), use_mask ? h->mask.row_ptr.data() : nullptr, use_mask ? h->mask.col.data() : nullptr,
+                                 undirected != 0, nsample, nodes);
+    const int64_t nchunk = (int64_t)c.chunk_node.size(), total = (int64_t)c.nb.size();
     std::vector<double> s_host(std::max<int64_t>(total, 1)); std::vector<int32_t> cnt_host(std::max<int64_t>(total, 1));
     h->last_kernel_ms = 0.0;
     if (nchunk > 0) {
         DevBuf<int32_t> dnb, dcn, dcc, dcnt; DevBuf<int64_t> dco; DevBuf<double> ds;
-        const float *dA = h->A, *dB = h->dB();
-        const int da = h->da, ld = h->ld;
-        const int64_t *dmrp = use_mask ? h->d_mask_row_ptr.get() : nullptr; const int32_t *dmcol = use_mask ? h->d_mask_col.get() : nullptr;
-        GEMHIP_CHECK(dnb.upload(nb.data(), total));
-        GEMHIP_CHECK(dcn.upload(chunk_node.data(), nchunk));
-        GEMHIP_CHECK(dcc.upload(chunk_cnt.data(), nchunk));
-        GEMHIP_CHECK(dco.upload(chunk_off.data(), nchunk));
+        GEMHIP_CHECK(dnb.upload(c.nb.data(), total));
+        GEMHIP_CHECK(dcn.upload(c.chunk_node.data(), nchunk));
+        GEMHIP_CHECK(dcc.upload(c.chunk_cnt.data(), nchunk));
+        GEMHIP_CHECK(dco.upload(c.chunk_off.data(), nchunk));
         GEMHIP_CHECK(ds.reserve(total)); GEMHIP_CHECK(dcnt.reserve(total));
-        const int nv = (da + WAVE - 1) / WAVE;
-#define EV_LAUNCH(NV, KIND) do { \
-            if (masked) hipLaunchKernelGGL((eval_ap_masked_kernel<NV, KIND>), dim3((unsigned)nchunk), dim3(EV_BLOCK), 0, 0, n, da, dA, dB, ld, (int)undirected, \
-                                           dcn.get(), dco.get(), dcc.get(), dnb.get(), dmrp, dmcol, ds.get(), dcnt.get()); \
-            else hipLaunchKernelGGL((eval_ap_kernel<NV, KIND>), dim3((unsigned)nchunk), dim3(EV_BLOCK), 0, 0, n, da, dA, dB, ld, (int)undirected, \
-                                    dcn.get(), dco.get(), dcc.get(), dnb.get(), ds.get(), dcnt.get()); } while (0)
-#define EV_LAUNCH_NV(KIND) do { if (nv <= 1) EV_LAUNCH(1, KIND); else if (nv <= 2) EV_LAUNCH(2, KIND); else if (nv <= 4) EV_LAUNCH(4, KIND); else EV_LAUNCH(8, KIND); } while (0)
-        GEMHIP_CHECK(timed_launch(&h->last_kernel_ms, [&] { if (h->kind == 0) EV_LAUNCH_NV(0); else EV_LAUNCH_NV(1); }));
-#undef EV_LAUNCH_NV
-#undef EV_LAUNCH
+        auto launch = [&](auto NV, auto KIND, auto MASKED) {
+            hipLaunchKernelGGL((eval_ap_kernel<decltype(NV)::value, decltype(KIND)::value, decltype(MASKED)::value>), dim3((unsigned)nchunk), dim3(EV_BLOCK), 0, 0,
+                               n, h->da, h->A.get(), h->dB(), h->ld, (int)undirected, dcn.get(), dco.get(), dcc.get(), dnb.get(), h->d_mask_row_ptr.get(),
+                               h->d_mask_col.get(), ds.get(), dcnt.get());
+        };
+        GEMHIP_CHECK(timed_launch(&h->last_kernel_ms, [&] {
+            dispatch_width(h->kind, h->da, [&](auto NV, auto KIND) { if (use_mask) launch(NV, KIND, std::true_type{}); else launch(NV, KIND, std::false_type{}); });
+        }));
         GEMHIP_CHECK(hipMemcpy(s_host.data(), ds, total * 8, hipMemcpyDeviceToHost));
         GEMHIP_CHECK(hipMemcpy(cnt_host.data(), dcnt, total * 4, hipMemcpyDeviceToHost));
     }
-    // ---- AP_i = mean over true neighbours with s > 0 of rank_hit / rank_all ; rank_hit = position among the neighbours in
-    //      the evaluator's order (score descending, node id ascending on ties), rank_all = 1 + the streamed count
-    std::vector<int64_t> ord;
-    for (int64_t k = 0; k < nsample; ++k) {
-        ord.clear();
-        for (int64_t e = node_off[k]; e < node_off[k + 1]; ++e) if (s_host[e] > 0.0) ord.push_back(e);
-        std::sort(ord.begin(), ord.end(), [&](int64_t x, int64_t y) { return s_host[x] > s_host[y] || (s_host[x] == s_host[y] && nb[x] < nb[y]); });
-        double sum = 0.0;
-        for (size_t r = 0; r < ord.size(); ++r) sum += (double)(r + 1) / (double)(1 + cnt_host[ord[r]]);
-        ap_out[k] = ord.empty() ? 0.0 : sum / (double)ord.size();
-        if (npos_out) npos_out[k] = (int64_t)ord.size();
-    }
+    ap_from_counts(nsample, c.nb.data(), c.node_off.data(), s_host.data(), cnt_host.data(), ap_out, npos_out);
     return GEMHIP_OK;
 }
 
@@ -526,30 +446,17 @@ extern "C" int gemhip_eval_set_mask(gemhip_eval_t h, const int64_t *mask_row_ptr
     GEMHIP_REQUIRE(h, "eval_set_mask: handle is null");
     if (!mask_row_ptr) {                                             // clear
         h->has_mask = false;
-        h->mask_row_ptr.clear(); h->mask_col.clear();
+        h->mask = EvalMask();
         h->d_mask_row_ptr.reset(); h->d_mask_col.reset();
         return GEMHIP_OK;
     }
-    const int64_t n = h->n;
-    GEMHIP_REQUIRE(mask_row_ptr[0] == 0, "eval_set_mask: row_ptr[0] is %lld, not 0", (long long)mask_row_ptr[0]);
-    for (int64_t i = 0; i < n; ++i) GEMHIP_REQUIRE(mask_row_ptr[i + 1] >= mask_row_ptr[i], "eval_set_mask: row_ptr decreases at row %lld", (long long)i);
-    const int64_t nnz = mask_row_ptr[n];
-    GEMHIP_REQUIRE(nnz == 0 || mask_col, "eval_set_mask: col is null");
-    for (int64_t e = 0; e < nnz; ++e) GEMHIP_REQUIRE(mask_col[e] >= 0 && mask_col[e] < n, "eval_set_mask: column %d outside [0,%lld)", mask_col[e], (long long)n);
-    // ---- the kernels walk a cursor through a row: ascending, each column once
-    std::vector<int64_t> rp(n + 1, 0); std::vector<int32_t> cl; cl.reserve(nnz);
-    for (int64_t i = 0; i < n; ++i) {
-        const size_t first = cl.size();
-        cl.insert(cl.end(), mask_col + mask_row_ptr[i], mask_col + mask_row_ptr[i + 1]);
-        std::sort(cl.begin() + first, cl.end());
-        cl.erase(std::unique(cl.begin() + first, cl.end()), cl.end());
-        rp[i + 1] = (int64_t)cl.size();
-    }
+    if (const EvalCsrError err = check_eval_csr(h->n, mask_row_ptr, mask_col, nullptr)) return refuse_csr("eval_set_mask", err, h->n, mask_row_ptr);
+    EvalMask m = normalise_mask(h->n, mask_row_ptr, mask_col);       // the kernels walk a cursor through a row: ascending, each column once
     DevBuf<int64_t> drp; DevBuf<int32_t> dcl;                        // uploaded first: a failed copy leaves the handle's mask as it was
-    GEMHIP_CHECK(drp.upload(rp.data(), rp.size()));
-    GEMHIP_CHECK(dcl.upload(cl.data(), cl.size()));
+    GEMHIP_CHECK(drp.upload(m.row_ptr.data(), m.row_ptr.size()));
+    GEMHIP_CHECK(dcl.upload(m.col.data(), m.col.size()));
     h->d_mask_row_ptr = std::move(drp); h->d_mask_col = std::move(dcl);
-    h->mask_row_ptr.swap(rp); h->mask_col.swap(cl);
+    h->mask = std::move(m);
     h->has_mask = true;
     return GEMHIP_OK;
 }
@@ -574,16 +481,14 @@ extern "C" int gemhip_eval_topk(gemhip_eval_t h, int32_t undirected, int32_t use
     const size_t total = (size_t)nsample * (size_t)k;
     GEMHIP_CHECK(dnodes.upload(nodes, nsample));
     GEMHIP_CHECK(did.reserve(total)); GEMHIP_CHECK(dscore.reserve(total)); GEMHIP_CHECK(dhit.reserve(total));
-    const int da = h->da, ld = h->ld;
-    const float *dA = h->A, *dB = h->dB();
-    const int nv = (da + WAVE - 1) / WAVE;
     const size_t lds = (size_t)TK_WAVES * k * (sizeof(double) + sizeof(int));
-#define TK_LAUNCH(NV, KIND) hipLaunchKernelGGL((eval_topk_kernel<NV, KIND>), dim3((unsigned)nsample), dim3(EV_BLOCK), lds, 0, n, da, dA, dB, ld, (int)undirected, \
-                                               dnodes.get(), (int)k, dmrp, dmcol, h->d_row_ptr.get(), h->d_col.get(), did.get(), dscore.get(), dhit.get())
-#define TK_LAUNCH_NV(KIND) do { if (nv <= 1) TK_LAUNCH(1, KIND); else if (nv <= 2) TK_LAUNCH(2, KIND); else if (nv <= 4) TK_LAUNCH(4, KIND); else TK_LAUNCH(8, KIND); } while (0)
-    GEMHIP_CHECK(timed_launch(&h->last_kernel_ms, [&] { if (h->kind == 0) TK_LAUNCH_NV(0); else TK_LAUNCH_NV(1); }));
-#undef TK_LAUNCH_NV
-#undef TK_LAUNCH
+    GEMHIP_CHECK(timed_launch(&h->last_kernel_ms, [&] {
+        dispatch_width(h->kind, h->da, [&](auto NV, auto KIND) {
+            hipLaunchKernelGGL((eval_topk_kernel<decltype(NV)::value, decltype(KIND)::value>), dim3((unsigned)nsample), dim3(EV_BLOCK), lds, 0, n, h->da, h->A.get(),
+                               h->dB(), h->ld, (int)undirected, dnodes.get(), (int)k, dmrp, dmcol, h->d_row_ptr.get(), h->d_col.get(), did.get(), dscore.get(),
+                               dhit.get());
+        });
+    }));
     GEMHIP_CHECK(hipMemcpy(id_out, did, total * sizeof(int32_t), hipMemcpyDeviceToHost));
     GEMHIP_CHECK(hipMemcpy(score_out, dscore, total * sizeof(double), hipMemcpyDeviceToHost));
     GEMHIP_CHECK(hipMemcpy(hit_out, dhit, total, hipMemcpyDeviceToHost));
@@ -610,30 +515,15 @@ extern "C" int gemhip_eval_pairs(gemhip_eval_t h, int64_t npairs, const int32_t 
     GEMHIP_CHECK(h->d_ed.upload(ed, npairs));
     GEMHIP_CHECK(h->d_score.reserve(npairs));
     if (hit_out) GEMHIP_CHECK(h->d_hit.reserve(npairs));
-    const int da = h->da, ld = h->ld;
-    const int nv = (da + 63) / 64;
-    const bool vec = ld % 4 == 0;
     const unsigned blocks = (unsigned)std::min<int64_t>((npairs + EP_BLOCK / EP_GROUP - 1) / (EP_BLOCK / EP_GROUP), EP_MAX_BLOCKS);
     uint8_t *dhit = hit_out ? h->d_hit.get() : nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    GEMHIP_CHECK(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(GEMHIP_E_HIP, "eval_pairs: hipEventCreate failed"); }
-    (void)hipEventRecord(e0, 0);
-#define EP_LAUNCH(KIND, VEC, NV) hipLaunchKernelGGL((eval_pairs_kernel<KIND, VEC, NV>), dim3(blocks), dim3(EP_BLOCK), 0, 0, da, ld, h->A.get(), h->dB(), \
-                                                    h->d_row_ptr.get(), h->d_col.get(), npairs, h->d_st.get(), h->d_ed.get(), h->d_score.get(), dhit)
-#define EP_LAUNCH_NV(KIND, VEC) do { if (nv <= 1) EP_LAUNCH(KIND, VEC, 1); else if (nv <= 2) EP_LAUNCH(KIND, VEC, 2); else if (nv <= 4) EP_LAUNCH(KIND, VEC, 4); else EP_LAUNCH(KIND, VEC, 8); } while (0)
-    if (h->kind == 0) { if (vec) EP_LAUNCH_NV(0, true); else EP_LAUNCH_NV(0, false); }
-    else              { if (vec) EP_LAUNCH_NV(1, true); else EP_LAUNCH_NV(1, false); }
-#undef EP_LAUNCH_NV
-#undef EP_LAUNCH
-    hipError_t e = hipGetLastError();
-    (void)hipEventRecord(e1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    GEMHIP_CHECK(e);
-    h->last_pairs_ms = ms;
+    auto launch = [&](auto NV, auto KIND, auto VEC) {
+        hipLaunchKernelGGL((eval_pairs_kernel<decltype(KIND)::value, decltype(VEC)::value, decltype(NV)::value>), dim3(blocks), dim3(EP_BLOCK), 0, 0, h->da, h->ld,
+                           h->A.get(), h->dB(), h->d_row_ptr.get(), h->d_col.get(), npairs, h->d_st.get(), h->d_ed.get(), h->d_score.get(), dhit);
+    };
+    GEMHIP_CHECK(timed_launch(&h->last_pairs_ms, [&] {
+        dispatch_width(h->kind, h->da, [&](auto NV, auto KIND) { if (h->ld % 4 == 0) launch(NV, KIND, std::true_type{}); else launch(NV, KIND, std::false_type{}); });
+    }));
     GEMHIP_CHECK(hipMemcpy(score_out, h->d_score, npairs * 8, hipMemcpyDeviceToHost));
     if (hit_out) GEMHIP_CHECK(hipMemcpy(hit_out, h->d_hit, npairs, hipMemcpyDeviceToHost));
     return GEMHIP_OK;

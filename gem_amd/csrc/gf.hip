@@ -1145,23 +1145,21 @@ extern "C" int gemhip_gf_train(int64_t n, int64_t m, const int32_t *src, const i
     int rc = gemhip_gf_plan_create(n, m, src, dst, w, d, 0, n, &p);
     if (rc) return rc;
     rc = gemhip_gf_plan_set_embedding(p, X_inout);
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    float ms = 0.f;
-    if (!rc && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess)) rc = fail(GEMHIP_E_HIP, "gf_train: hipEventCreate");
+    EventMarks<2> t;
+    double ms = 0.0;
+    if (!rc && t.create() != hipSuccess) rc = fail(GEMHIP_E_HIP, "gf_train: hipEventCreate");
     if (!rc) {
-        hipEventRecord(t0, 0);
+        (void)t.mark(0);
         rc = gemhip_gf_plan_sweeps(p, max_iter, eta, regu, nullptr);
-        hipEventRecord(t1, 0);
+        (void)t.mark(1);
     }
     if (!rc) rc = gemhip_gf_plan_get_embedding(p, X_inout);
-    if (!rc) hipEventElapsedTime(&ms, t0, t1);
+    if (!rc) (void)t.ms(0, 1, &ms);
     phase_acc()[PH_KERNELS] = ms * 1e-3;
     if (stats && !rc) {
         stats[0] = ms * 1e-3; stats[1] = (double)p->nupd; stats[2] = (double)p->nrows;
         stats[3] = (double)(p->level_off.size() - 1);
     }
-    if (t0) hipEventDestroy(t0);
-    if (t1) hipEventDestroy(t1);
     gemhip_gf_plan_destroy(p);
     phase_acc()[PH_TOTAL] = phase_now() - t_call;
     return rc;

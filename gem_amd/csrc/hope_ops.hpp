@@ -119,16 +119,11 @@ struct SpmmTimer {           // HIP events around a run of back-to-back SpMM lau
     }
     ~SpmmTimer() { if (idx != (size_t)-1) hipEventRecord(H.sp_pool[idx + 1], H.s); }       // no host wait here: spmm_time_collect() reads the pairs
 };
-// The two events around a solve (device window, stats[0]); owns them the way Buf owns memory.  create() also arms the SpMM timers.
-struct SolveEvents {
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    SolveEvents() = default;
-    SolveEvents(const SolveEvents &) = delete;
-    SolveEvents &operator=(const SolveEvents &) = delete;
-    ~SolveEvents() { if (ev0) hipEventDestroy(ev0); if (ev1) hipEventDestroy(ev1); }
+// The two marks around a solve (device window, stats[0]).  create() also arms the SpMM timers.
+struct SolveEvents : EventMarks<2> {
     int create(Hope &H, bool time_spmm)
     {
-        if (!H.err) { HOPE_TRY(H, hipEventCreate(&ev0)); HOPE_TRY(H, hipEventCreate(&ev1)); H.time_spmm = time_spmm; }
+        if (!H.err) { HOPE_TRY(H, EventMarks<2>::create()); H.time_spmm = time_spmm; }
         return H.err;
     }
 };

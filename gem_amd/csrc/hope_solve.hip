@@ -44,8 +44,9 @@ void emit(Hope &H, const float *basis, int ld, int mc, const std::vector<double>
 // Closes the solve's device window and its SpMM timers and fills stats[] (the arguments from `terms` on: fill_solve_stats).  Returns the window in ms.
 float finish_solve(Hope &H, SolveEvents &tm, double *stats, double terms, double basis, double cycles, double change, double br, double residual)
 {
-    float ms = 0.f;
-    if (!H.err) { hipEventRecord(tm.ev1, H.s); hipEventSynchronize(tm.ev1); hipEventElapsedTime(&ms, tm.ev0, tm.ev1); }
+    double window = 0.0;
+    if (!H.err) { (void)tm.mark(1, H.s); (void)tm.ms(0, 1, &window); }
+    const float ms = (float)window;
     if (!H.err) spmm_time_collect(H); else H.sp_used = 0;
     if (stats && !H.err) fill_solve_stats(stats, ms, H.spmm_count, H.spmm_cols, terms, basis, cycles, change, br, residual, H.spmm_ms);
     return ms;
@@ -67,7 +68,7 @@ int krylov_svd(Hope &H, int64_t n, int32_t k, int32_t oversample, int32_t krylov
     dalloc(Vall, ldm); dalloc(Ball, ldm); dalloc(T0, ldb); dalloc(T1, ldb); dalloc(W0, ldb); dalloc(Tmp, ldm);
     SolveEvents tm;                 // (declared after the buffers: destroyed before they are freed, on every way out)
     if (tm.create(H, stats != nullptr)) return H.err;
-    hipEventRecord(tm.ev0, H.s);
+    (void)tm.mark(0, H.s);
 
     randn(H, Vall, b, ldm, seed);
     int m0 = orth(H, Vall, ldm, b, Tmp, ldm, 1e-10);
@@ -297,7 +298,7 @@ int sym_filter_svd(Hope &H, int kind, int64_t n, int32_t k, int32_t oversample, 
     walloc(4, &F[2], (size_t)n * ldv); walloc(5, &Tmp, (size_t)n * ldv); walloc(6, &colv, 512);
     SolveEvents tm;
     if (tm.create(H, stats != nullptr)) return H.err;
-    hipEventRecord(tm.ev0, H.s);
+    (void)tm.mark(0, H.s);
     const auto ht1 = std::chrono::steady_clock::now();
 
     randn(H, Vall, b, ldv, seed);

@@ -469,32 +469,26 @@ extern "C" int gemhip_n2v_train(int64_t n, int64_t nnz, const int64_t *row_ptr, 
     gemhip_n2v_t h = nullptr;
     int rc = gemhip_n2v_create(n, nnz, row_ptr, col, w, &h);
     if (rc) return rc;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (auto &e : ev) if (!rc && hipEventCreate(&e) != hipSuccess) rc = fail(GEMHIP_E_HIP, "n2v_train: hipEventCreate");
+    EventMarks<4> ev;
+    if (ev.create() != hipSuccess) rc = fail(GEMHIP_E_HIP, "n2v_train: hipEventCreate");
     const int64_t nwalks = h->m_start * (int64_t)num_walks;
-    if (!rc) { hipEventRecord(ev[0], 0); rc = gemhip_n2v_walks(h, p, q, num_walks, walk_len, seed, flags, 0, nwalks, nullptr); }
+    if (!rc) { (void)ev.mark(0); rc = gemhip_n2v_walks(h, p, q, num_walks, walk_len, seed, flags, 0, nwalks, nullptr); }
     if (!rc) rc = gemhip_n2v_vocab(h, nullptr);
-    if (!rc) { hipEventRecord(ev[1], 0); rc = (flags & GEMHIP_N2V_VOCAB_ORDER) ? gemhip_n2v_build_unigram_vocab_order(h, flags, nullptr, nullptr, nullptr, nullptr)
-                                                                                 : gemhip_n2v_build_unigram(h, nullptr, nullptr, nullptr); }
+    if (!rc) { (void)ev.mark(1); rc = (flags & GEMHIP_N2V_VOCAB_ORDER) ? gemhip_n2v_build_unigram_vocab_order(h, flags, nullptr, nullptr, nullptr, nullptr)
+                                                                         : gemhip_n2v_build_unigram(h, nullptr, nullptr, nullptr); }
     if (!rc) rc = gemhip_sgns_init(h, d, seed, nullptr, nullptr);
-    if (!rc) hipEventRecord(ev[2], 0);
+    if (!rc) (void)ev.mark(2);
     for (int ep = 0; !rc && ep < epochs; ++ep)
         rc = gemhip_sgns_train(h, window, SGNS_NEG, 0.025f, epochs, ep, 0, nwalks, nwalks * walk_len, (int64_t)ep * nwalks * walk_len,
                                seed, flags, nullptr);
-    if (!rc) { hipEventRecord(ev[3], 0); rc = gemhip_sgns_get_tables(h, X_out, nullptr); }
-    if (!rc && stats) {
-        float a = 0, b = 0;
-        hipEventElapsedTime(&a, ev[0], ev[1]);
-        hipEventElapsedTime(&b, ev[2], ev[3]);
-        stats[0] = a * 1e-3; stats[1] = b * 1e-3; stats[2] = (double)nwalks * walk_len; stats[3] = h->uniform_rows ? 1.0 : 0.0;
-    }
+    if (!rc) { (void)ev.mark(3); rc = gemhip_sgns_get_tables(h, X_out, nullptr); }
     if (!rc) {     // kernel seconds of the call (HIP events): walks + vocabulary, then table init + SGNS
-        float a = 0, b = 0;
-        hipEventElapsedTime(&a, ev[0], ev[1]);
-        hipEventElapsedTime(&b, ev[2], ev[3]);
+        double a = 0.0, b = 0.0;
+        (void)ev.ms(0, 1, &a);
+        (void)ev.ms(2, 3, &b);
+        if (stats) { stats[0] = a * 1e-3; stats[1] = b * 1e-3; stats[2] = (double)nwalks * walk_len; stats[3] = h->uniform_rows ? 1.0 : 0.0; }
         phase_acc()[PH_KERNELS] = (a + b) * 1e-3;
     }
-    for (auto &e : ev) if (e) hipEventDestroy(e);
     gemhip_n2v_destroy(h);
     phase_acc()[PH_TOTAL] = phase_now() - t_call;
     return rc;

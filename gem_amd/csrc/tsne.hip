@@ -47,13 +47,6 @@ constexpr int REP_TARGET_GRID = 1024;                 // workgroups wanted: four
 constexpr int SUM_BLOCK = 1024;
 constexpr double MACHINE_EPS = 2.220446049250313e-16; // np.finfo(np.double).eps, the clamp of sklearn's _kl_divergence
 
-__device__ __forceinline__ double wave_sum_f64(double v)   // butterfly: the same bits in every lane
-{
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // ================================================================== centring
 // part[s][c] = sum over the rows of slab s of X[.][c]
 __global__ __launch_bounds__(256) void tsne_colsum_kernel(const float *__restrict__ X, int64_t n, int d, int64_t ld, int64_t rows_per_slab,
@@ -522,20 +515,9 @@ __global__ __launch_bounds__(256) void tsne_reset_kernel(int64_t n, float2 *__re
 // ================================================================== host side
 unsigned grid_of(int64_t count, int per) { return (unsigned)((count + per - 1) / per < 1 ? 1 : (count + per - 1) / per); }
 
-struct Stopwatch {                                      // two events on the null stream, owned
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Stopwatch() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t start() { hipError_t e = a ? hipSuccess : hipEventCreate(&a); if (e == hipSuccess && !b) e = hipEventCreate(&b); return e != hipSuccess ? e : hipEventRecord(a, 0); }
-    hipError_t stop(double *ms)                         // waits for the stream
-    {
-        hipError_t e = hipEventRecord(b, 0);
-        if (e == hipSuccess) e = hipEventSynchronize(b);
-        float f = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&f, a, b);
-        *ms = f;
-        return e;
-    }
-};
+using Stopwatch = EventMarks<2>;                        // start and stop marks on the null stream, made on first use
+hipError_t start(Stopwatch &w) { const hipError_t e = w.create(); return e != hipSuccess ? e : w.mark(0); }
+hipError_t stop(Stopwatch &w, double *ms) { const hipError_t e = w.mark(1); return e != hipSuccess ? e : w.ms(0, 1, ms); }      // waits for the stream
 
 int check_matrix(const char *who, int64_t n, int32_t d, int32_t ld, const float *X)
 {
@@ -685,19 +667,19 @@ extern "C" int gemhip_tsne_create(int64_t n, int32_t d, int32_t ld, const float 
     GEMHIP_CHECK(h->id.reserve((size_t)n * k));
     GEMHIP_CHECK(h->p.reserve((size_t)n * k));
     GEMHIP_CHECK(dist.reserve((size_t)n * k));
-    GEMHIP_CHECK(h->watch.start());
+    GEMHIP_CHECK(start(h->watch));
     rc = knn_device(dX, n, d, ld, k, h->id, dist);
     if (rc) return rc;
-    GEMHIP_CHECK(h->watch.stop(&h->ms[0]));
+    GEMHIP_CHECK(stop(h->watch, &h->ms[0]));
     dX.reset();
-    GEMHIP_CHECK(h->watch.start());
+    GEMHIP_CHECK(start(h->watch));
     hipLaunchKernelGGL(tsne_affinity_kernel, dim3(grid_of(n, 4)), dim3(256), 0, 0, dist.get(), n, k, perplexity, h->p.get());
     GEMHIP_CHECK(hipGetLastError());
-    GEMHIP_CHECK(h->watch.stop(&h->ms[1]));
-    GEMHIP_CHECK(h->watch.start());
+    GEMHIP_CHECK(stop(h->watch, &h->ms[1]));
+    GEMHIP_CHECK(start(h->watch));
     rc = build_transpose(h.get());
     if (rc) return rc;
-    GEMHIP_CHECK(h->watch.stop(&h->ms[2]));
+    GEMHIP_CHECK(stop(h->watch, &h->ms[2]));
     rc = alloc_iteration_state(h.get());
     if (rc) return rc;
     *out = h.release();
@@ -752,7 +734,7 @@ extern "C" int gemhip_tsne_run(gemhip_tsne_t h, int32_t n_iter, double exaggerat
     GEMHIP_REQUIRE(std::isfinite(exaggeration) && exaggeration > 0.0 && std::isfinite(momentum) && std::isfinite(lr),
                    "tsne_run: exaggeration = %g, momentum = %g, lr = %g", exaggeration, momentum, lr);
     const int64_t n = h->n;
-    GEMHIP_CHECK(h->watch.start());
+    GEMHIP_CHECK(start(h->watch));
     for (int32_t it = 0; it < n_iter; ++it) {
         const bool last = it == n_iter - 1;
         const int rc = enqueue_gradient(h, exaggeration, last);
@@ -762,7 +744,7 @@ extern "C" int gemhip_tsne_run(gemhip_tsne_t h, int32_t n_iter, double exaggerat
     }
     hipLaunchKernelGGL(tsne_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, 0, h->gnrow.get(), n, h->scal.get() + 2);
     GEMHIP_CHECK(hipGetLastError());
-    GEMHIP_CHECK(h->watch.stop(&h->ms[3]));
+    GEMHIP_CHECK(stop(h->watch, &h->ms[3]));
     double s[3];
     GEMHIP_CHECK(hipMemcpy(s, h->scal, sizeof s, hipMemcpyDeviceToHost));
     if (kl_out) *kl_out = s[1];

@@ -5,7 +5,8 @@ It compares digests and resource numbers only -- no assembly text is kept.  One 
 
     python scripts/compare_kernel_isa.py <parent checkout> [<branch checkout, default: this tree>] [--out profiles/n2v_split_isa.json]
 
-Exit status 1 when a kernel of the parent is missing from the branch or differs.  Needs hipcc, no GPU.  profiles/n2v_split_isa.json was made this way."""
+A kernel missing by name in one tree whose digest and figures equal those of a kernel missing by name in the other is listed as `renamed` and does
+not count as different.  Exit status 1 when a kernel of the parent is missing from the branch or differs.  Needs hipcc, no GPU.  profiles/n2v_split_isa.json was made this way."""
 import hashlib
 import json
 import os
@@ -44,6 +45,7 @@ def unit_kernels(src, workdir):
         line = line.split(';')[0].strip()                    # comments carry no instruction
         if not line or line.startswith(('.p2align', '.cfi_', '.loc', '.file')):
             continue
+        line = line.replace(name, '<this kernel>')           # (its .amdhsa_kernel block and section name: a renamed kernel keeps its digest)
         body.append(re.sub(r'\.L(BB|tmp|func_begin|JTI)\d+_?', r'.L\1_', line))     # function-local labels are numbered by position in the unit
     cur = None
     for line in text:                                        # amdhsa.kernels metadata: one `.name:` per kernel, its figures around it
@@ -83,6 +85,16 @@ def is_library(name):
     return name.startswith('_ZN7rocprim')                   # hipcub's sort: one instantiation per target architecture it knows, none of the project's text
 
 
+def match_renamed(parent, branch, row):
+    """{parent name: branch name} of kernels that changed name only: missing by name on either side, with equal digest and resource figures.
+    Kernels that share those figures (the same body under several names) are paired in sorted order."""
+    gone, new = {}, {}
+    for side, other, out in ((parent, branch, gone), (branch, parent, new)):
+        for k in sorted(set(side) - set(other)):
+            out.setdefault(json.dumps(row(side[k])), []).append(k)
+    return {p: b for key in gone for p, b in zip(gone[key], new.get(key, []))}
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else None
@@ -91,7 +103,10 @@ def main():
     parent, branch = tree_kernels(args[0]), tree_kernels(args[1] if len(args) > 1 else ROOT)
     row = lambda k: None if k is None else [k[f] for f in FIELDS]
     rows, bad, lib = {}, [], {'parent': hashlib.sha256(), 'branch': hashlib.sha256(), 'count': 0}
+    renamed = match_renamed(parent, branch, row)
     for k in sorted(set(parent) | set(branch)):
+        if k in renamed or k in renamed.values():
+            continue
         p, b = parent.get(k), branch.get(k)
         same = p is not None and row(p) == row(b)
         if p is not None and not same:
@@ -105,8 +120,9 @@ def main():
         else:
             rows[k] = {'parent': row(p) and row(p) + [p['unit']], 'branch': row(b) and row(b) + [b['unit']]}
     moved = sorted(k for k in parent if k in branch and parent[k]['unit'] != branch[k]['unit'] and not is_library(k))
-    summary = {'kernels_parent': len(parent), 'kernels_branch': len(branch), 'identical': len(parent) - len(bad), 'changed_unit': moved,
-               'missing_or_different': bad, 'only_in_branch': sorted(set(branch) - set(parent)),
+    summary = {'kernels_parent': len(parent), 'kernels_branch': len(branch), 'identical': len(parent) - len(bad) - len(renamed), 'changed_unit': moved,
+               'renamed': [{'parent': p, 'branch': b, 'figures': row(parent[p])} for p, b in sorted(renamed.items())],
+               'missing_or_different': bad, 'only_in_branch': sorted(set(branch) - set(parent) - set(renamed.values())),
                'library_kernels_identical': {'count': lib['count'], 'sha256_over_all_parent': lib['parent'].hexdigest(), 'sha256_over_all_branch': lib['branch'].hexdigest()}}
     if out:
         with open(out, 'w') as f:

@@ -6,8 +6,8 @@
 Workload: an SBM graph (default 1M nodes / 10M arcs), split_di_graph_to_train_test at 0.8 (undirected, np.random.seed(--seed)), GF trained on
 the TRAIN graph, `--nodes` nodes from eligible_sample of the TEST graph.  On ONE evaluator handle (test CSR + trained table, train graph as
 mask), after one warm-up round, three rounds of
-  ap_ms          gemhip_eval_ap          eval_ap_kernel, the unmasked stream: the baseline
-  ap_masked_ms   gemhip_eval_ap_masked   eval_ap_masked_kernel: the same rows plus a walk through one mask row per node
+  ap_ms          gemhip_eval_ap          eval_ap_kernel<NV, KIND, false>, the unmasked stream: the baseline
+  ap_masked_ms   gemhip_eval_ap_masked   eval_ap_kernel<NV, KIND, true>: the same rows plus a walk through one mask row per node
   topk_ms        gemhip_eval_topk        eval_topk_kernel at k = --k
 each a HIP-event time of the kernel alone (gemhip_eval_last_kernel_ms).  `masked_over_ap` is the ratio of the medians, `ap_spread` and
 `ap_masked_spread` are (max - min) / median of the three repeats.  Also recorded: the link-prediction MAP (mean masked AP of the sample) of the

@@ -1,6 +1,7 @@
 """Device-free references, inputs and DERIVED bounds for the three reporting instruments:
 
-  eval_ap_kernel<NV, KIND>   (gem_amd/csrc/eval.hip)   sampled AP               -> test_eval_ap_gpu.py
+  eval_ap_kernel<NV, KIND, MASKED>  (gem_amd/csrc/eval.hip)  sampled AP        -> test_eval_ap_gpu.py, test_link_prediction_gpu.py;
+                             its host half (gem_amd/csrc/eval_host.hip) on the CPU  -> test_eval_host.py
   gf_objective_kernel        (gem_amd/csrc/gf.hip)     f1, f2 of gf.cpp:94-113  -> test_gf_objective_gpu.py
   svd_error_impl             (gem_amd/csrc/hope.hip)   `SVD error (low rank)`   -> test_hope_svd_error_gpu.py
 
@@ -13,7 +14,7 @@ from gem_amd.graph import to_csr
 # ====================================================================================================================== sampled AP
 AP_N = 700
 AP_HUB, AP_512, AP_513, AP_EMPTY, AP_LOWER, AP_TWICE, AP_FAR = 2, 5, 9, 11, 650, 20, 333
-# (da, pad, kind, split): every eval_ap_kernel<NV, KIND> instantiation, the `cc < da` tail on either side of every NV boundary, ld > da
+# (da, pad, kind, split): every eval_ap_kernel<NV, KIND, false> instantiation, the `cc < da` tail on either side of every NV boundary, ld > da
 # (ld = da + 3 at two widths, ld = da + 1 at an even one), the two HOPE splits (A != B), and the distance kernel
 AP_CASES = [(da, {63: 3, 257: 3, 128: 1}.get(da, 0), 0, False) for da in (1, 63, 64, 65, 128, 129, 182, 256, 257, 509, 512)] + \
            [(91, 0, 0, True), (200, 0, 0, True)] + [(da, 0, 1, False) for da in (63, 65, 182, 257, 512)]
@@ -110,7 +111,7 @@ def ap_reference_is_clear_of_ties(score, mag, da):
 
 
 def ap_kernel_scores(A, B, da, kind, i, drop_last_column=False):
-    """Row i of the score matrix in eval_ap_kernel's own arithmetic: lane l sums the terms of columns l, l + 64, ... in fp64 in that order,
+    """Row i of the score matrix in the arithmetic of eval.hip's RowScore (the one row score of the AP and top-k kernels): lane l sums the terms of columns l, l + 64, ... in fp64 in that order,
     wave_sum_f64 folds the 64 partial sums by the butterfly 32, 16, ..., 1.  drop_last_column plants a tail mask that is one short."""
     width = da - 1 if drop_last_column else da
     a = A[i, :width].astype(np.float64); b = (A if B is None else B)[:, :width].astype(np.float64)

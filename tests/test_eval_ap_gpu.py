@@ -1,4 +1,4 @@
-"""GPU: gemhip_eval_ap at EVERY eval_ap_kernel<NV, KIND> instantiation (NV = 1, 2, 4, 8; inner product and distance kernel), node by node against
+"""GPU: gemhip_eval_ap at EVERY eval_ap_kernel<NV, KIND, false> instantiation (NV = 1, 2, 4, 8; inner product and distance kernel), node by node against
 gr.average_precision_rows on the dense fp64 score matrix of the same fp32 inputs, with and without `undirected`, over all 700 nodes of
 instrument_refs.ap_graph (a hub of 600 = two chunks, rows of 512 and 513, an empty row, a row of lower ids only, an unsorted row that lists a
 column twice).  Widths on either side of every NV boundary and tail mask, ld > da with 1e30 in the padding, HOPE splits wider than 16.

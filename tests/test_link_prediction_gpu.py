@@ -1,4 +1,4 @@
-"""GPU: link prediction on the evaluator handle of gem_amd/csrc/eval.hip -- gemhip_eval_set_mask, gemhip_eval_ap_masked (eval_ap_masked_kernel)
+"""GPU: link prediction on the evaluator handle of gem_amd/csrc/eval.hip -- gemhip_eval_set_mask, gemhip_eval_ap_masked (eval_ap_kernel<NV, KIND, MASKED>)
 and gemhip_eval_topk (eval_topk_kernel) -- node by node over all 700 nodes of instrument_refs.ap_graph with the train mask of linkpred_refs
 (an empty mask row on the hub, a mask row longer than a chunk, a node whose candidates are exactly its positives, a node with every positive
 masked, an unsorted row with a duplicate, a masked self-loop, a row of lower ids only), against link_prediction_rows and the stable host order
