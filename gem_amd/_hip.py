@@ -129,6 +129,17 @@ _SIGS = {
     'gemhip_tsne_affinities': (C.c_int, [C.c_int64, C.c_int32, f32p, C.c_double, f32p]),
     'gemhip_tsne_set_affinities': (C.c_int, [C.c_void_p, i32p, f32p]),
     'gemhip_tsne_gradient': (C.c_int, [C.c_void_p, C.c_double, f32p, f64p, f64p]),
+    'gemhip_nc_create': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_void_p)]),
+    'gemhip_nc_set_labels': (C.c_int, [C.c_void_p, C.c_int32, i64p, i32p]),
+    'gemhip_nc_fit': (C.c_int, [C.c_void_p, C.c_int64, i32p, C.c_double, C.c_double, C.c_int32, f64p, f64p]),
+    'gemhip_nc_set_weights': (C.c_int, [C.c_void_p, f64p]),
+    'gemhip_nc_scores': (C.c_int, [C.c_void_p, C.c_int64, i32p, f64p]),
+    'gemhip_nc_predict_topk': (C.c_int, [C.c_void_p, C.c_int64, i32p, i32p, C.POINTER(C.c_uint8), i64p, i64p]),
+    'gemhip_nc_last_ms': (C.c_int, [C.c_void_p, f64p]),
+    'gemhip_nc_info': (C.c_int, [C.c_void_p, i64p]),
+    'gemhip_nc_destroy': (C.c_int, [C.c_void_p]),
+    'gemhip_nc_pass': (C.c_int, [C.c_void_p, C.c_int64, i32p, C.c_double, f64p, f64p, f64p, f64p]),
+    'gemhip_nc_newton_step_host': (C.c_int, [C.c_int32, f64p, f64p, f64p, f64p, f64p]),
     'gemhip_n2v_train': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_uint64, C.c_int32, f32p, f64p]),
     'gemhip_n2v_create': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.POINTER(C.c_void_p)]),

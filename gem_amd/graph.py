@@ -207,6 +207,15 @@ def sbm_graph(n, n_directed_edges, n_blocks, seed, intra=0.8):
     return EdgeListGraph(n, src[perm].astype(np.int32), dst[perm].astype(np.int32), None)
 
 
+def sbm_block_labels(n, n_blocks):
+    """The block of every node of sbm_graph(n, ..., n_blocks, ...): arange(n) // (n // n_blocks), int32.  When n_blocks does not divide n the
+    trailing n % n_blocks nodes, which sbm_graph leaves isolated, count to the last block."""
+    bs = n // n_blocks
+    if bs < 2:
+        raise ValueError('blocks too small')
+    return np.minimum(np.arange(n, dtype=np.int64) // bs, n_blocks - 1).astype(np.int32)
+
+
 def orient_randomly(g, seed):
     """A DIRECTED graph from an undirected one stored in both directions: every undirected edge {a, b} is kept in ONE direction chosen
     by a fair coin (half the arcs).  HOPE's general case (hope.py:28-36 makes no symmetry assumption): A != A^T, S has distinct left

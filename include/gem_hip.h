@@ -685,6 +685,54 @@ int gemhip_tsne_affinities(int64_t n, int32_t k, const float *dist, double perpl
 int gemhip_tsne_set_affinities(gemhip_tsne_t h, const int32_t *id, const float *p);
 int gemhip_tsne_gradient(gemhip_tsne_t h, double exaggeration, float *grad_out, double *kl_out, double *z_out);
 
+/* ------------------------------------------- node classification (one-vs-rest L2 logistic regression, top-k ranker)
+ * Replaces: GEM's fourth evaluation task, sklearn's OneVsRestClassifier(LogisticRegression()) on embedding rows with the "top-k ranker" of the
+ * embedding literature.  The scheme: for every class c independently the minimiser over theta = (w, b) of
+ *     F_c = C * sum_{i in T} log(1 + exp(-y_ic (x_i . w + b))) + |w|^2 / 2,   y_ic = +-1,   the intercept unpenalised
+ * (sklearn LogisticRegression(penalty='l2', C, fit_intercept=True), any solver but liblinear), by damped Newton: one device pass over the
+ * training rows gives loss, gradient and Hessian of a block of classes, the host solves the (d+1) x (d+1) systems by fp64 Cholesky (Levenberg
+ * shift when a pivot is not positive) and runs an Armijo line search (c1 = 1e-4, halving) on device loss evaluations.  A class is converged
+ * after the step whose decrement lambda^2 = -g . delta is at most dec_tol * max(1, F_c).  No floating-point atomics: identical bits on every run.
+ *
+ * gemhip_nc_create: X_host [n][ld] float32, uploaded once; 1 <= d <= ld, n >= 1, every X[i][c < d] finite (GEMHIP_E_INVALID, the first
+ * offender named); d <= 255 and n < 2^31 (GEMHIP_E_UNSUPPORTED).  Everything is checked on the host before any device call.
+ * gemhip_nc_set_labels: the multi-label indicator as a CSR of class ids per node, row_ptr [n + 1], cls [row_ptr[n]]; 1 <= K <= 65536 and
+ * row_ptr[n] < 2^31 (GEMHIP_E_UNSUPPORTED beyond).  row_ptr[0] == 0, no negative row, ids in [0, K), no class twice in a row: GEMHIP_E_INVALID,
+ * the first offender named by position.  Rows need not be sorted.  Forgets the handle's weights.
+ * gemhip_nc_fit: train_idx [n_train] rows in [0, n), any order, a repeated row counts twice.  C > 0 and dec_tol > 0 finite, max_iter >= 1.
+ * W_inout [K][d + 1] fp64, w then b: the start on input (finite), the result on output; the handle keeps it for prediction.  A class with no
+ * positive among the training rows, or no negative, has no finite minimiser: w = 0, b = -inf / +inf, no iteration.  info_out (may be NULL)
+ * [K][6] = {iterations, backtracks, |g|_inf and lambda^2 at the last iterate a pass evaluated, converged (1 / 0; 1 for a degenerate class),
+ * degenerate (-1 no positive, +1 no negative, 0)}.  A class that does not converge in max_iter iterations is returned as it is, flagged.
+ * gemhip_nc_set_weights: W [K][d + 1] for prediction without a fit; w finite, b not NaN (+-inf is a constant predictor).
+ * gemhip_nc_scores: out [m][K] fp64 logits x_i . w_c + b_c of the rows idx [m].
+ * gemhip_nc_predict_topk: for row t the k_t classes of largest logit, ties to the lower class id; k_t = the row's number of labels when
+ * k_or_null is NULL, otherwise 0 <= k[t] <= K (GEMHIP_E_INVALID naming t).  pred_or_null [m][K] 0 / 1.  counts_out [3][K] = TP, FP, FN per
+ * class over the rows (integer atomics: exact), *exact_out = rows whose predicted set equals the true set. */
+typedef struct gemhip_nc *gemhip_nc_t;
+int gemhip_nc_create(int64_t n, int32_t d, int32_t ld, const float *X_host, gemhip_nc_t *out);
+int gemhip_nc_set_labels(gemhip_nc_t h, int32_t K, const int64_t *row_ptr, const int32_t *cls);
+int gemhip_nc_fit(gemhip_nc_t h, int64_t n_train, const int32_t *train_idx, double C, double dec_tol, int32_t max_iter, double *W_inout,
+                  double *info_out /* or NULL */);
+int gemhip_nc_set_weights(gemhip_nc_t h, const double *W);
+int gemhip_nc_scores(gemhip_nc_t h, int64_t m, const int32_t *idx, double *out);
+int gemhip_nc_predict_topk(gemhip_nc_t h, int64_t m, const int32_t *idx, const int32_t *k_or_null, uint8_t *pred_or_null, int64_t *counts_out,
+                           int64_t *exact_out);
+/* Milliseconds: out[4] = {upload (host wall), the last fit (host wall), mean Newton pass of that fit (host wall, kernels + copy back),
+ * the last predict (HIP events)}. */
+int gemhip_nc_last_ms(gemhip_nc_t h, double *out);
+/* out[8] = {n, d, K, Newton passes, loss evaluations and iterations of the last fit, classes per block, rows per LDS slab}. */
+int gemhip_nc_info(gemhip_nc_t h, int64_t *out);
+int gemhip_nc_destroy(gemhip_nc_t h);
+/* Stages on their own (tests).
+ * gemhip_nc_pass: one kernel pass as the solver makes it, for all K classes at W [K][d + 1] (finite): F_out [K], g_out [K][d + 1],
+ * H_out [K][d + 1][d + 1] -- the objective above, its gradient and its full symmetric Hessian, regulariser included.
+ * gemhip_nc_newton_step_host: host only, works without a device.  Solves (H + shift I) delta = -g by fp64 Cholesky on the upper triangle of
+ * H [d1][d1]; shift = 0 unless a pivot is not positive, then 1e-10 * max(1, max |H_jj|) times 10 per retry.  *dec_out = -g . delta;
+ * *shift_out (may be NULL) = the shift used.  GEMHIP_E_NOTCONVERGED if no shift helps or an input is not finite. */
+int gemhip_nc_pass(gemhip_nc_t h, int64_t n_train, const int32_t *train_idx, double C, const double *W, double *F_out, double *g_out, double *H_out);
+int gemhip_nc_newton_step_host(int32_t d1, const double *H, const double *g, double *delta_out, double *dec_out, double *shift_out /* or NULL */);
+
 #ifdef __cplusplus
 }
 #endif
