@@ -140,6 +140,16 @@ _SIGS = {
     'gemhip_nc_destroy': (C.c_int, [C.c_void_p]),
     'gemhip_nc_pass': (C.c_int, [C.c_void_p, C.c_int64, i32p, C.c_double, f64p, f64p, f64p, f64p]),
     'gemhip_nc_newton_step_host': (C.c_int, [C.c_int32, f64p, f64p, f64p, f64p, f64p]),
+    'gemhip_kmeans_create': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_void_p)]),
+    'gemhip_kmeans_seed_pp': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, f64p, i32p, f32p]),
+    'gemhip_kmeans_fit': (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_double, C.c_int32, i32p, f64p]),
+    'gemhip_kmeans_assign': (C.c_int, [C.c_void_p, C.c_int32, f32p, i32p, f32p]),
+    'gemhip_kmeans_update': (C.c_int, [C.c_void_p, C.c_int32, i32p, f32p, i64p]),
+    'gemhip_kmeans_contingency': (C.c_int, [C.c_void_p, C.c_int32, i32p, i64p]),
+    'gemhip_clustering_scores_host': (C.c_int, [i64p, C.c_int32, C.c_int32, f64p]),
+    'gemhip_kmeans_last_ms': (C.c_int, [C.c_void_p, f64p]),
+    'gemhip_kmeans_info': (C.c_int, [C.c_void_p, i64p]),
+    'gemhip_kmeans_destroy': (C.c_int, [C.c_void_p]),
     'gemhip_n2v_train': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_uint64, C.c_int32, f32p, f64p]),
     'gemhip_n2v_create': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.POINTER(C.c_void_p)]),

@@ -2,5 +2,6 @@ from gem_amd.evaluation.reconstruction import (evaluateStaticGraphReconstruction
                                                random_edge_pairs, sampled_ap_gpu)
 from gem_amd.evaluation.link_prediction import (evaluateStaticLinkPrediction, evaluate_link_prediction_gpu, link_prediction_dense,  # noqa: F401
                                                 link_prediction_rows)
+from gem_amd.evaluation.clustering import KMeans, clustering_scores, evaluateClustering, expClustering  # noqa: F401
 from gem_amd.evaluation.node_classification import (NodeClassifier, evaluateNodeClassification, expNC, f1_from_counts, label_csr,  # noqa: F401
                                                     split_nodes)

@@ -733,6 +733,53 @@ int gemhip_nc_destroy(gemhip_nc_t h);
 int gemhip_nc_pass(gemhip_nc_t h, int64_t n_train, const int32_t *train_idx, double C, const double *W, double *F_out, double *g_out, double *H_out);
 int gemhip_nc_newton_step_host(int32_t d1, const double *H, const double *g, double *delta_out, double *dec_out, double *shift_out /* or NULL */);
 
+/* ------------------------------------------- k-means and community-recovery scores (Lloyd, k-means++, NMI / ARI / purity)
+ * Replaces: sklearn.cluster.KMeans(algorithm='lloyd') on embedding rows and sklearn.metrics' normalized_mutual_info_score /
+ * adjusted_rand_score against planted communities.  The scheme: the semantics are sklearn 1.7.2's on the float32 matrix,
+ * restated exactly where sklearn leaves an order open.  Assign: the fp32 score |c_k|^2 - 2 x_i . c_k on the matrix units, a running minimum per
+ * row, ties to the lower cluster id.  Update: integer counts, fp64 sums in a fixed order, centre = float32(sum / count).  Empty clusters:
+ * the j-th empty cluster in ascending id takes the row of j-th largest fp64 squared distance to the OLD centre of its label (ties: the lower
+ * row id); the row leaves its donor's sum and count; that iteration's labels stay.  Stop: labels equal to the previous iteration's (strict),
+ * else sum |c_new - c_old|^2 <= tol * mean(var(X, axis=0)), else max_iter; after a non-strict stop one more assign, so that the labels belong to
+ * the returned centres.  Inertia: sum_i |x_i - c_label(i)|^2, the difference form, fp64.  No floating-point atomics: identical bytes on
+ * every run.
+ *
+ * Refused on the host before any device call, the first offender named by position -- GEMHIP_E_INVALID: n < 1, d < 1, ld < d, a non-finite
+ * X[i][c < d], K < 1, K > n, a non-finite centre, max_iter < 1, tol < 0 or not finite, n_trials < 1, a u outside [0, 1), a label outside
+ * [0, K), a true label outside [0, Kt), gemhip_kmeans_contingency before any labels exist; GEMHIP_E_UNSUPPORTED: n >= 2^31, d > 256, K > 16384,
+ * n_trials > 16, a contingency table of more than 2^26 entries.  gemhip_kmeans_fit returns GEMHIP_E_UNSUPPORTED (nothing divided by zero) when a
+ * relocation would leave the donor cluster without a row.
+ *
+ * gemhip_kmeans_create: X_host [n][ld] float32, uploaded once, zero-padded to a multiple of 8 columns.
+ * gemhip_kmeans_seed_pp: sklearn's greedy k-means++ on host-supplied uniforms u [K][n_trials] in [0, 1).  Centre 0 is row
+ * min(floor(u[0][0] n), n - 1).  Centre c > 0: candidate t is searchsorted(cumsum_fp64(D2), u[c][t] * total, side='right') clipped to n - 1, D2
+ * the running minimum of the fp32 difference-form squared distances to the chosen rows, the cumulative sum in row order; the candidate of
+ * smallest fp64 potential sum_i min(D2_i, |x_i - x_cand|^2) wins, ties to the lower t.  chosen_idx_out [K], centres_out [K][d].
+ * gemhip_kmeans_fit: centres_inout [K][d] float32, the start on input, the result on output; labels_out [n]; info_out (may be NULL) [6] =
+ * {inertia, iterations, strict (1 / 0), rows relocated, the last sum |c_new - c_old|^2, tol * mean(var(X, axis=0))}.
+ * gemhip_kmeans_assign: one assign step; labels_out [n], score_out_or_null [n] the fp32 score of the chosen centre.
+ * gemhip_kmeans_update: one update step of labels [n] without relocation: centres_out [K][d] (zeros for an empty cluster), counts_out [K].
+ * gemhip_kmeans_contingency: table_out [K][Kt] int64 (integer atomics: exact) of the labels the last fit, assign or update left on the device
+ * against labels_true [n] in [0, Kt).
+ * gemhip_clustering_scores_host: host only, works without a device.  out [4] = {NMI with the arithmetic mean of the entropies (1 when both
+ * partitions are a single cluster, as sklearn), ARI in sklearn's pair-count form (128-bit integers: n^2 at n = 2^31 fits), purity,
+ * homogeneity}, all fp64 from table [Kp][Kt]; empty rows and columns are legal, a negative entry or an empty table is GEMHIP_E_INVALID. */
+typedef struct gemhip_kmeans *gemhip_kmeans_t;
+int gemhip_kmeans_create(int64_t n, int32_t d, int32_t ld, const float *X_host, gemhip_kmeans_t *out);
+int gemhip_kmeans_seed_pp(gemhip_kmeans_t h, int32_t K, int32_t n_trials, const double *u, int32_t *chosen_idx_out, float *centres_out);
+int gemhip_kmeans_fit(gemhip_kmeans_t h, int32_t K, float *centres_inout, double tol, int32_t max_iter, int32_t *labels_out, double *info_out /* or NULL */);
+int gemhip_kmeans_assign(gemhip_kmeans_t h, int32_t K, const float *centres, int32_t *labels_out, float *score_out_or_null);
+int gemhip_kmeans_update(gemhip_kmeans_t h, int32_t K, const int32_t *labels, float *centres_out, int64_t *counts_out);
+int gemhip_kmeans_contingency(gemhip_kmeans_t h, int32_t Kt, const int32_t *labels_true, int64_t *table_out);
+int gemhip_clustering_scores_host(const int64_t *table, int32_t Kp, int32_t Kt, double *out);
+/* Milliseconds: out[6] = {upload (host wall), the last seeding (host wall), the last fit's iterations (HIP events), that over its iteration
+ * count, the last gemhip_kmeans_assign's kernel (HIP events), the last gemhip_kmeans_update (HIP events, its copies included)}. */
+int gemhip_kmeans_last_ms(gemhip_kmeans_t h, double *out);
+/* out[12] = {n, d, d padded to 8, K of the labels on the device (0: none), rows per assign workgroup (128), centres per tile (32), the caps on
+ * d (256), K (16384) and n_trials (16), members per sum slice (512), rows per counting-sort slab, iterations of the last fit}. */
+int gemhip_kmeans_info(gemhip_kmeans_t h, int64_t *out);
+int gemhip_kmeans_destroy(gemhip_kmeans_t h);
+
 #ifdef __cplusplus
 }
 #endif
