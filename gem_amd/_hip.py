@@ -150,6 +150,18 @@ _SIGS = {
     'gemhip_kmeans_last_ms': (C.c_int, [C.c_void_p, f64p]),
     'gemhip_kmeans_info': (C.c_int, [C.c_void_p, i64p]),
     'gemhip_kmeans_destroy': (C.c_int, [C.c_void_p]),
+    'gemhip_rank_argsort': (C.c_int, [C.c_int64, f64p, i32p]),
+    'gemhip_rank_binary': (C.c_int, [C.c_int64, f64p, C.POINTER(C.c_uint8), f64p, i64p]),
+    'gemhip_rank_curve': (C.c_int, [C.c_int64, f64p, C.POINTER(C.c_uint8), C.c_int64, f64p, i64p, i64p, i64p]),
+    'gemhip_rank_binary_from_groups_host': (C.c_int, [C.c_int64, i64p, i64p, f64p, i64p]),
+    'gemhip_rank_info': (C.c_int, [i64p]),
+    'gemhip_edgeclf_create': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_void_p)]),
+    'gemhip_edgeclf_features': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, i32p, i32p, f32p]),
+    'gemhip_edgeclf_scores': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, i32p, i32p, f64p, f64p]),
+    'gemhip_edgeclf_fit': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, i32p, i32p, C.POINTER(C.c_uint8), C.c_double, C.c_double, C.c_int32, f64p, f64p]),
+    'gemhip_edgeclf_last_ms': (C.c_int, [C.c_void_p, f64p]),
+    'gemhip_edgeclf_info': (C.c_int, [C.c_void_p, i64p]),
+    'gemhip_edgeclf_destroy': (C.c_int, [C.c_void_p]),
     'gemhip_n2v_train': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_uint64, C.c_int32, f32p, f64p]),
     'gemhip_n2v_create': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.POINTER(C.c_void_p)]),

@@ -27,6 +27,7 @@
 //   K  <= NC_MAX_K = 65536  the top-k kernel walks a row's K logits once per predicted label
 //   n  <  2^31              row ids are int32; a row list (n_train, m) is below 2^31 too
 #include "common.hpp"
+#include "nc_device.hpp"
 #include "nc_host.hpp"
 #include <algorithm>
 #include <chrono>
@@ -449,6 +450,29 @@ extern "C" int gemhip_nc_create(int64_t n, int32_t d, int32_t ld, const float *X
     h->n = n; h->ld = ld; h->d = d; h->d1 = d + 1; h->dp = (d + 1 + 31) & ~31;
     const double t0 = wall_ms();
     GEMHIP_CHECK(h->X.upload(X_host, (size_t)n * ld));
+    GEMHIP_CHECK(hipDeviceSynchronize());
+    h->ms[0] = wall_ms() - t0;
+    const int rc = set_lds_limit(h->dp);
+    if (rc) return rc;
+    *out = h.release();
+    return GEMHIP_OK;
+}
+
+// nc_device.hpp: the same handle from a matrix on the device.  Additive: gemhip_nc_create above keeps its own path.
+int gemhip::nc_create_from_device(int64_t n, int32_t d, int64_t ld, const float *X_dev, gemhip_nc_t *out)
+{
+    GEMHIP_REQUIRE(out != nullptr, "nc_create_from_device: NULL output");
+    *out = nullptr;
+    GEMHIP_REQUIRE(n >= 1, "nc_create_from_device: n = %lld (need n >= 1)", (long long)n);
+    GEMHIP_REQUIRE(d >= 1 && ld >= d, "nc_create_from_device: d = %d, ld = %lld (need 1 <= d <= ld)", d, (long long)ld);
+    if (n > INT32_MAX) return fail(GEMHIP_E_UNSUPPORTED, "nc_create_from_device: n = %lld: must be below 2^31", (long long)n);
+    if (d > NC_MAX_D) return fail(GEMHIP_E_UNSUPPORTED, "nc_create_from_device: d = %d: at most %d (one LDS slab of the padded rows)", d, NC_MAX_D);
+    GEMHIP_REQUIRE(X_dev != nullptr, "nc_create_from_device: NULL X");
+    std::unique_ptr<gemhip_nc> h(new gemhip_nc);
+    h->n = n; h->ld = ld; h->d = d; h->d1 = d + 1; h->dp = (d + 1 + 31) & ~31;
+    const double t0 = wall_ms();
+    GEMHIP_CHECK(h->X.reserve((size_t)n * ld));
+    GEMHIP_CHECK(hipMemcpy(h->X, X_dev, (size_t)n * ld * sizeof(float), hipMemcpyDeviceToDevice));
     GEMHIP_CHECK(hipDeviceSynchronize());
     h->ms[0] = wall_ms() - t0;
     const int rc = set_lds_limit(h->dp);

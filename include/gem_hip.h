@@ -780,6 +780,68 @@ int gemhip_kmeans_last_ms(gemhip_kmeans_t h, double *out);
 int gemhip_kmeans_info(gemhip_kmeans_t h, int64_t *out);
 int gemhip_kmeans_destroy(gemhip_kmeans_t h);
 
+/* ------------------------------------------- binary ranking metrics: a device sort, ROC-AUC, average precision, the curve points
+ * Replaces: sklearn.metrics roc_auc_score / average_precision_score / roc_curve / precision_recall_curve on host arrays of fp64 scores and
+ * 0 / 1 labels.  The scheme: a stable LSD radix sort of order-preserving 64-bit keys, descending, -0.0 tied with +0.0,
+ * +-inf ordinary keys, the int32 position as payload; eight 8-bit passes, a pass whose digit histogram has one non-empty bucket skipped.  Tie
+ * groups end where two neighbouring keys differ; an integer scan of the labels gives the cumulative tp, fp at each group end.
+ *     U2  = sum_g pos_g (2 (N - fp_g) + neg_g)           twice the Mann-Whitney U, an exact int64
+ *     auc = U2 / (2 P N)                                  one fp64 division, correctly rounded while both integers are below 2^53
+ *     ap  = (1 / P) sum_g pos_g tp_g / (tp_g + fp_g)      sklearn's step-wise average precision, fp64 terms summed in a fixed order
+ * No floating-point atomics; integer atomics only in histograms; identical bytes on every run.
+ *
+ * Refused on the host before any device call -- GEMHIP_E_INVALID: m < 1, a NaN score (named by position), a label that is neither 0 nor 1
+ * (named by position), only one class present (the message says which is missing); GEMHIP_E_UNSUPPORTED: m >= 2^31.
+ *
+ * gemhip_rank_argsort: perm_out [m], the stable descending permutation: what numpy.argsort(-score, kind='stable') returns.
+ * gemhip_rank_binary: out [4] = {auc, ap, prevalence P / m, kernel milliseconds (HIP events around the launches; allocations and copies excluded)};
+ * counts [4] = {P, N, the number T of distinct scores, U2}.
+ * gemhip_rank_curve: thr_out / tp_out / fp_out [T], the threshold and the cumulative counts at each distinct score, descending; *T_out = T
+ * is always written once the inputs pass; cap < T is GEMHIP_E_INVALID and nothing else is written.
+ * gemhip_rank_binary_from_groups_host: host only, works without a device.  The same out and counts (out[3] = 0) from the group table tp / fp [T];
+ * a table that is not cumulative (a group without a member, a decreasing count, a total of 2^31 or more) is GEMHIP_E_INVALID naming the group.
+ * gemhip_rank_info: out [8] = {keys per sort workgroup W, threads per workgroup, bits per pass, passes run and passes skipped by the last
+ * sort on this thread, its workgroups, T of the last group table, m}. */
+int gemhip_rank_argsort(int64_t m, const double *score, int32_t *perm_out);
+int gemhip_rank_binary(int64_t m, const double *score, const uint8_t *label, double *out, int64_t *counts);
+int gemhip_rank_curve(int64_t m, const double *score, const uint8_t *label, int64_t cap, double *thr_out, int64_t *tp_out, int64_t *fp_out, int64_t *T_out);
+int gemhip_rank_binary_from_groups_host(int64_t T, const int64_t *tp, const int64_t *fp, double *out, int64_t *counts);
+int gemhip_rank_info(int64_t *out);
+
+/* ------------------------------------------- link prediction as classification: pair features and the pair classifier
+ * Replaces: the protocol of node2vec section 4.4 on the host -- a binary operator on the two embedding rows of a node pair, sklearn's
+ * LogisticRegression on the pair features, ROC-AUC on held-out pairs.  Operators (op), on rows a = X[st], b = X[ed], in fp32 without FMA
+ * contraction, bit-equal to the same numpy float32 expressions:
+ *     0 average (a + b) * 0.5f     1 Hadamard a * b     2 L1 fabsf(a - b)     3 L2 t = a - b rounded, then t * t
+ *
+ * gemhip_edgeclf_create: X_host [n][ld] float32, uploaded once; 1 <= d <= ld, n >= 1, every X[i][c < d] finite and at most 1e18 in magnitude
+ * (GEMHIP_E_INVALID, the first offender named: every operator's result is then finite); d <= 255 and n < 2^31 (GEMHIP_E_UNSUPPORTED).
+ * Pairs: st / ed [m] node ids in [0, n) (GEMHIP_E_INVALID naming the first pair outside), 1 <= m < 2^31; st == ed and repeated pairs are legal.
+ * Everything is checked on the host before any device call.
+ * gemhip_edgeclf_features: F_out [m][d] float32.
+ * gemhip_edgeclf_scores: score_out [m] fp64 = sum_j (double)F[p][j] * w[j] + w[d], gather, operator and reduction fused, no feature matrix
+ * formed, a fixed summation order.  w [d + 1] finite (the intercept not NaN); w == NULL: the plain inner product sum_j (double)a_j (double)b_j
+ * (op is then ignored).
+ * gemhip_edgeclf_fit: label [m] in {0, 1}; builds the feature matrix on the device and fits the one-class problem "is an edge" with the
+ * node-classification solver (gemhip_nc_fit: C, dec_tol, max_iter as there).  w_inout [d + 1], weights then intercept: the start on input
+ * (finite), the minimiser on output.  info_out (may be NULL) [8] = gemhip_nc_fit's six per-class fields {iterations, backtracks, |g|_inf,
+ * lambda^2, converged, degenerate}, then the Newton passes and the loss evaluations.  A fit that does not converge in max_iter iterations
+ * returns its iterate, flagged; labels of one class only give the degenerate answer of gemhip_nc_fit.  Device memory at the peak:
+ * 2 * m * d * 4 bytes (the feature matrix and the solver's copy; the former is freed before the first pass). */
+typedef struct gemhip_edgeclf *gemhip_edgeclf_t;
+int gemhip_edgeclf_create(int64_t n, int32_t d, int32_t ld, const float *X_host, gemhip_edgeclf_t *out);
+int gemhip_edgeclf_features(gemhip_edgeclf_t h, int32_t op, int64_t m, const int32_t *st, const int32_t *ed, float *F_out);
+int gemhip_edgeclf_scores(gemhip_edgeclf_t h, int32_t op, int64_t m, const int32_t *st, const int32_t *ed, const double *w /* or NULL */, double *score_out);
+int gemhip_edgeclf_fit(gemhip_edgeclf_t h, int32_t op, int64_t m, const int32_t *st, const int32_t *ed, const uint8_t *label, double C, double dec_tol,
+                       int32_t max_iter, double *w_inout, double *info_out /* or NULL */);
+/* Milliseconds: out[6] = {upload (host wall), the last features kernel, the last scores kernel (HIP events), the last fit (host wall), that
+ * fit's mean Newton pass (host wall), its feature kernel (HIP events)}. */
+int gemhip_edgeclf_last_ms(gemhip_edgeclf_t h, double *out);
+/* out[8] = {n, d, pairs a wave has in flight, pairs per workgroup, Newton passes, loss evaluations and iterations of the last fit, m of the
+ * last call}. */
+int gemhip_edgeclf_info(gemhip_edgeclf_t h, int64_t *out);
+int gemhip_edgeclf_destroy(gemhip_edgeclf_t h);
+
 #ifdef __cplusplus
 }
 #endif
