@@ -30,20 +30,20 @@ def _walks_of(b, l):
     return walks
 
 
-@pytest.mark.parametrize('d,parts,bucket,flags,hogwild_path,segments', [(16, 4, (1, 0), 9, 0, False), (128, 2, (0, 1), 11, 0, False), (7, 3, (2, 2), 9, 0, True),
-                                                                      (128, 2, (1, 1), 11, 1, True), (64, 5, (3, 1), 11, 9, False), (129, 2, (0, 1), 11, 1, False)])
-def test_train_part_deterministic_matches_oracle(sbm1024, d, parts, bucket, flags, hogwild_path, segments):
-    """gemhip_sgns_train_part (sgns_win_kernel<PART>) on ONE wavefront == TrainModel in walk order restricted to the bucket (context partition,
-    word partition) -- oracle_sgns_train_part, the restatement of ELF @0x40d6a0 with the partition filter -- to the 2e-4 of the unpartitioned
-    test.  hogwild_path 1 runs the Hogwild instantiation (delta write-back, reload-on-update, atomic centre row) on the one wavefront, 9 the same
-    with every node of >= 30 tokens hot (never in the LDS window, negatives by atomic add).  segments: the corpus as two shards of unequal
-    length with their own walk ids (the N-rank layout), including a padded tail."""
+HOT_THR = 15       # corpus of the bucket tests (SBM-1024, walks 100..356 of 40 tokens, seed 3): largest token count 23, mean 10
+
+
+def _bucket_case(sbm1024, d, parts, bucket, flags, hogwild_path, segments, fresh=0, local_key=False):
+    """One bucket launch on ONE wavefront against oracle_sgns_train_part (see the tests below).  hogwild_path 9: hot rows from HOT_THR tokens on, with the
+    fresh bits `fresh`; local_key: the hot nodes carry the key INT32_MAX in the count buffer instead (threshold INT32_MAX).  Before a launch with hot rows
+    the pairs of the bucket are classified on the CPU (tests/sgns_path_refs.py): at least 5 % of them in each class the case is there for."""
+    import sgns_path_refs as spr
     n, src, dst, b = backend(sbm1024, d)
     l = 40
     b.walks(1.0, 1.0, 1, l, 3, flags, 100, 356)
     walks = _walks_of(b, l)
     b.vocab(); b.build_unigram_parts(parts)
-    counts = b.counts.cpu().numpy()
+    counts = b.counts.cpu().numpy().copy()
     UT, KT, off = oracle.unigram_build_parts(counts, parts)
     UTd = np.empty(n, np.float32); KTd = np.empty(n, np.int32)
     _hip.check(b.L.gemhip_n2v_build_unigram_parts(b.h, parts, _hip.ptr(UTd, C.c_float), _hip.ptr(KTd, C.c_int32)))
@@ -53,10 +53,22 @@ def test_train_part_deterministic_matches_oracle(sbm1024, d, parts, bucket, flag
     rows = P.shape[0]
     Np = (0.05 * torch.randn((rows, d), generator=torch.Generator().manual_seed(1))).to(P.device)
     Po, No = P.cpu().numpy().copy(), Np.cpu().numpy().copy()
+    thr = 0
     if hogwild_path:
         _hip.check(b.L.gemhip_sgns_set_window_cache(b.h, -1, 1))
         if hogwild_path == 9:
-            _hip.check(b.L.gemhip_sgns_set_hot_rows(b.h, 30))
+            assert counts.max() == 23 and HOT_THR < counts.max()
+            thr = spr.INT32_MAX if local_key else HOT_THR
+            key = np.where(counts >= HOT_THR, spr.INT32_MAX, counts).astype(np.int32) if local_key else counts
+            wids = np.concatenate([100 + np.arange(150), 250 + np.arange(106)]) if segments else 100 + np.arange(256)
+            cls = spr.pair_classes(walks, 5, 3, 0, UT[off[gj]:off[gj + 1]], KT[off[gj]:off[gj + 1]], off[gj + 1] - off[gj], key, thr, fresh=fresh, flags=flags,
+                                   wids=wids, bucket=(parts, gi, gj))
+            s = spr.assert_floors(cls, ('fast_hot', 'fast_cold', 'slow', 'hot_ctx') + (('hot_word',) if (fresh & 1) or local_key else ()))
+            print({k: round(float(v), 4) for k, v in s.items()})
+            if local_key:      # the key a Hogwild launch would see, in the buffer the library reads the counts from (the tables above were built from the counts)
+                b.counts.copy_(torch.from_numpy(key)); torch.cuda.synchronize()
+            _hip.check(b.L.gemhip_sgns_set_hot_rows(b.h, thr))
+            _hip.check(b.L.gemhip_sgns_set_fresh(b.h, fresh))
     dev = P.device
     if segments:      # shard 0 = walks [0, 150) with ids 100.., shard 1 = walks [150, 256) with ids 250..; work items 2 x 150 (44 of them absent)
         corpus = torch.from_numpy(walks).to(dev)
@@ -73,10 +85,45 @@ def test_train_part_deterministic_matches_oracle(sbm1024, d, parts, bucket, flag
         want_pairs = oracle.sgns_train_part(walks, None, 5, 0.025, 256 * l, 0, 0, parts, gi, gj, UT[off[gj]:off[gj + 1]], KT[off[gj]:off[gj + 1]], 3, flags,
                                             Po, No, walk_id_offset=100, local_rows=True)
     torch.cuda.synchronize()
+    if hogwild_path:
+        k, wv, hot, fr = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        _hip.check(b.L.gemhip_sgns_last_launch(b.h, C.byref(k), C.byref(wv), C.byref(hot), C.byref(fr)))
+        assert (k.value, wv.value, hot.value, fr.value) == (2, 1, thr, fresh if thr else 0)
     assert b.pairs() == want_pairs > 100
+    if thr:
+        assert want_pairs == s['pairs']
     for got, want in ((P.cpu().numpy(), Po), (Np.cpu().numpy(), No)):
-        assert np.abs(got - want).max() <= 2e-4 * np.abs(want).max() + 1e-6
+        err, scale = np.abs(got - want).max(), np.abs(want).max()
+        print('max|got - want| = %.3e, bar %.3e' % (err, 2e-4 * scale + 1e-6))
+        assert err <= 2e-4 * scale + 1e-6
     b.close()
+
+
+@pytest.mark.parametrize('d,parts,bucket,flags,hogwild_path,segments', [(16, 4, (1, 0), 9, 0, False), (128, 2, (0, 1), 11, 0, False), (7, 3, (2, 2), 9, 0, True),
+                                                                      (128, 2, (1, 1), 11, 1, True), (64, 5, (3, 1), 11, 9, False), (129, 2, (0, 1), 11, 1, False)])
+def test_train_part_deterministic_matches_oracle(sbm1024, d, parts, bucket, flags, hogwild_path, segments):
+    """gemhip_sgns_train_part (sgns_win_kernel<PART>) on ONE wavefront == TrainModel in walk order restricted to the bucket (context partition,
+    word partition) -- oracle_sgns_train_part, the restatement of ELF @0x40d6a0 with the partition filter -- to the 2e-4 of the unpartitioned
+    test.  hogwild_path 1 runs the Hogwild instantiation (delta write-back, reload-on-update, atomic centre row) on the one wavefront, 9 the same
+    with every node of >= HOT_THR = 15 tokens hot (never in the LDS window, negatives by atomic add): of the bucket's 2 264 pairs 67 % take the fast path
+    with a hot negative, 9 % without one, 24 % the slow path, 16 % have a hot context -- asserted from the CPU classifier before the launch.  (Up to here
+    the threshold was 30 on a corpus whose largest token count is 23: no node was hot and the launch never entered a hot branch.)  segments: the corpus as
+    two shards of unequal length with their own walk ids (the N-rank layout), including a padded tail."""
+    _bucket_case(sbm1024, d, parts, bucket, flags, hogwild_path, segments)
+
+
+@pytest.mark.parametrize('d,parts,bucket,segments,fresh,local_key', [(64, 5, (3, 1), False, 3, False),          # the case above with both fresh bits (whole-walk mode)
+                                                                     (128, 2, (0, 1), False, 0, False), (128, 2, (0, 1), False, 3, False),      # FULL, sliding window
+                                                                     (129, 2, (0, 1), False, 0, False), (129, 2, (0, 1), False, 3, False),      # <1, 4>: the `< dg` guards
+                                                                     (96, 3, (2, 0), True, 3, False),           # segment table: walk ids per shard, counts by GLOBAL id v * parts + part
+                                                                     (64, 5, (3, 1), False, 0, True)])          # the locally-hot key INT32_MAX in the count buffer
+def test_train_part_hot_and_fresh_rows_match_oracle(sbm1024, d, parts, bucket, segments, fresh, local_key):
+    """The hot-row and fresh-row branches of the bucket kernel (sgns_win_kernel<.., PART> with DELTA, RELOAD, !ALLC) on ONE wavefront against
+    oracle_sgns_train_part at 2e-4: nodes of >= 15 tokens hot as contexts (never cached, neu1e by atomic add), as negatives (atomic add of g * xc; bit 1:
+    re-fetched before the dot products) and, under bit 0 or with the key INT32_MAX, as centre words (returning atomic add, no closing add).  Shares of the
+    bucket's pairs by the CPU classifier at threshold 15 -- fast path with a hot negative / without / slow path, hot centre, hot context:
+    5 partitions (3, 1): 67 / 9 / 24 %, 21 %, 16 %;  2 partitions (0, 1): 67 / 17 / 16 %, 17 %, 16 %;  3 partitions (2, 0), two shards: 64 / 17 / 19 %, 15 %, 15 %."""
+    _bucket_case(sbm1024, d, parts, bucket, 11, 9, segments, fresh=fresh, local_key=local_key)
 
 
 def test_train_part_with_one_partition_is_train(sbm1024):
