@@ -382,7 +382,9 @@ void lap_edge_values(int64_t n, const int64_t *row_ptr, const int32_t *col, cons
     for (int64_t i = 0; i < n; ++i) {
         double deg = 0.0;
         for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) deg += w ? w[e] : 1.0;
-        dinv[i] = deg > 0.0 ? 1.0 / std::sqrt(deg) : 0.0;       // networkx: isolated nodes get 0
+        // zero-degree nodes: D^-1/2 = 0, so in T = I + M they sit at 1 (eigenvalue 1 of L_sym, not the 0 of networkx's all-zero row).  That is what the
+        // reference's ARPACK call returns -- zero rows at these nodes -- while every wanted eigenvalue is below 1 (tests/README_lap_lle.md)
+        dinv[i] = deg > 0.0 ? 1.0 / std::sqrt(deg) : 0.0;
     }
     for (int64_t i = 0; i < n; ++i)
         for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) va[e] = (float)(dinv[i] * (w ? w[e] : 1.0) * dinv[col[e]]);

@@ -15,14 +15,20 @@ from gem_amd.embedding.static_graph_embedding import StaticGraphEmbedding
 
 
 def symmetric_arrays(graph):
-    """(n, src, dst, w) of graph.to_undirected() with both directions listed, indexed by position in graph.nodes."""
+    """(n, src, dst, w) of graph.to_undirected() with both directions listed, indexed by position in graph.nodes.
+
+    An EdgeListGraph gets the weights networkx's DiGraph.to_undirected() keeps for graph.to_networkx(): for the pair {lo, hi} the arc hi -> lo
+    wins where it is listed (its source comes later in the node order), else lo -> hi; of several listings of the winning arc, and of a
+    self-loop, the last one wins.  Pairs come out sorted by (lo, hi)."""
     if isinstance(graph, EdgeListGraph):
         n = graph.n
         s, d = graph.src.astype(np.int64), graph.dst.astype(np.int64)
         w = np.ones(len(s), np.float32) if graph.w is None else graph.w
-        lo, hi = np.minimum(s, d), np.maximum(s, d)
-        key, first = np.unique(lo * n + hi, return_index=True)
-        lo, hi, w = key // n, key % n, w[first]
+        key = np.minimum(s, d) * n + np.maximum(s, d)
+        order = np.lexsort((s > d, key))                    # stable: by pair, lo -> hi before hi -> lo, listing order within each
+        key = key[order]
+        last = np.flatnonzero(np.append(key[1:] != key[:-1], True)[:len(key)])       # the last entry of each pair is the winner
+        lo, hi, w = key[last] // n, key[last] % n, w[order[last]]
     else:
         und = graph.to_undirected()
         n = len(und.nodes)

@@ -105,8 +105,14 @@ def align_signs(X, Xref, d):
 
 def lap_eigmap_dense(n, src, dst, w, d):
     """gem/embedding/lap.py:21-37 with a dense symmetric eigensolver: the d+1 smallest eigenpairs of
-    L_sym = I - D^-1/2 A D^-1/2 (nx.normalized_laplacian_matrix: isolated nodes get D^-1/2 = 0), X = v[:, 1:].
-    src/dst/w: the SYMMETRIC adjacency (both directions listed)."""
+    L_sym = I - D^-1/2 A D^-1/2, X = v[:, 1:].  src/dst/w: the SYMMETRIC adjacency (both directions listed).
+
+    Zero-degree nodes get D^-1/2 = 0 and keep the identity's 1: operator eigenvalue 1 with the node's unit vector, a zero row in every other
+    vector.  This is NOT nx.normalized_laplacian_matrix, whose row for such a node is all zero (eigenvalue 0).  It is what the reference's
+    eigs(L, k=d+1, which='SM') -- ARPACK without shift-invert -- returns while every wanted eigenvalue is below 1: the first product with L
+    removes those nodes from the Krylov space for good, so their rows come out exactly zero (tests/golden/ref_lap_edges.npz, pinned by
+    tests/test_lap_lle_refs.py).  The two diverge once an eigenvalue >= 1 is wanted, or when the Krylov space is the whole space and ARPACK
+    does find the node at 0 (the 6-node edge-case graph: tests/README_lap_lle.md)."""
     A = np.zeros((n, n))
     A[np.asarray(src), np.asarray(dst)] = np.asarray(w, dtype=np.float64)
     deg = A.sum(axis=1)
