@@ -162,6 +162,16 @@ _SIGS = {
     'gemhip_edgeclf_last_ms': (C.c_int, [C.c_void_p, f64p]),
     'gemhip_edgeclf_info': (C.c_int, [C.c_void_p, i64p]),
     'gemhip_edgeclf_destroy': (C.c_int, [C.c_void_p]),
+    'gemhip_nbr_create': (C.c_int, [C.c_int64, C.c_int64, i32p, i32p, C.POINTER(C.c_void_p)]),
+    'gemhip_nbr_degrees': (C.c_int, [C.c_void_p, i32p]),
+    'gemhip_nbr_weights': (C.c_int, [C.c_void_p, C.c_int32, f64p]),
+    'gemhip_nbr_scores': (C.c_int, [C.c_void_p, C.c_int64, i32p, i32p, C.c_int32, i32p, f64p, f64p, f64p, f64p]),
+    'gemhip_nbr_last_ms': (C.c_int, [C.c_void_p, f64p]),
+    'gemhip_nbr_info': (C.c_int, [C.c_void_p, i64p]),
+    'gemhip_nbr_destroy': (C.c_int, [C.c_void_p]),
+    'gemhip_nbr_graph_host': (C.c_int, [C.c_int64, C.c_int64, i32p, i32p, i64p, i32p, i32p]),
+    'gemhip_nbr_weights_host': (C.c_int, [C.c_int64, i32p, C.c_int32, f64p]),
+    'gemhip_nbr_plan_host': (C.c_int, [C.c_int64, i32p, C.c_int64, i32p, i32p, i64p]),
     'gemhip_n2v_train': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_float, C.c_uint64, C.c_int32, f32p, f64p]),
     'gemhip_n2v_create': (C.c_int, [C.c_int64, C.c_int64, i64p, i32p, f32p, C.POINTER(C.c_void_p)]),

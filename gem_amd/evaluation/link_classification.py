@@ -13,6 +13,7 @@ import numpy as np
 
 from gem_amd import _hip
 from gem_amd.evaluation import ranking
+from gem_amd.evaluation.link_heuristics import HEURISTICS, NeighbourScorer
 from gem_amd.evaluation.node_classification import DEC_TOL, MAX_ITER
 
 OPERATORS = {'average': 0, 'hadamard': 1, 'l1': 2, 'l2': 3}
@@ -205,8 +206,9 @@ class EdgeClassifier(object):
                 'pairs_per_wave': int(out[2]), 'pairs_per_workgroup': int(out[3]), 'newton_iterations': int(out[6])}
 
 
-def _score_pairs(ec, pairs, op, C, graph_embedding, X, test_graph):
-    """(scores of the test pairs, w or None, info or None, fit seconds, scoring seconds)."""
+def _score_pairs(ec, pairs, op, C, graph_embedding, X, test_graph, train_graph=None):
+    """(scores of the test pairs, w or None, info or None, fit seconds, scoring seconds).  train_graph: the graph a neighbourhood score
+    (HEURISTICS) is computed on, or an open NeighbourScorer of it; ec and X are not consulted then."""
     st, ed, _ = pairs['test']
     t0 = time.perf_counter()
     w = info = None
@@ -225,13 +227,22 @@ def _score_pairs(ec, pairs, op, C, graph_embedding, X, test_graph):
         n, tsrc, tdst, _, _ = edge_arrays(test_graph)
         with _DeviceEvaluator(n, tsrc, tdst, graph_embedding, X) as ev:
             score, _ = ev.pairs(st, ed, want_hit=False)
+    elif op in HEURISTICS:
+        if train_graph is None:
+            raise ValueError('op=%r needs train_graph' % (op,))
+        if isinstance(train_graph, NeighbourScorer):
+            score = train_graph.scores(st, ed, (op,))[op]
+        else:
+            with NeighbourScorer(train_graph) as ns:
+                score = ns.scores(st, ed, (op,))[op]
+        score = np.asarray(score, dtype=np.float64)
     else:
-        raise ValueError("op = %r: one of %s, 'dot', 'method'" % (op, ', '.join(FEATURE_OPS)))
+        raise ValueError("op = %r: one of %s, 'dot', 'method'; or a neighbourhood score without an embedding: %s" % (op, ', '.join(FEATURE_OPS), ', '.join(HEURISTICS)))
     return score, w, info, t1 - t0, time.perf_counter() - t1
 
 
-def _evaluate(ec, pairs, op, C, graph_embedding, X, test_graph, sample_s):
-    score, w, info, fit_s, score_s = _score_pairs(ec, pairs, op, C, graph_embedding, X, test_graph)
+def _evaluate(ec, pairs, op, C, graph_embedding, X, test_graph, sample_s, train_graph=None):
+    score, w, info, fit_s, score_s = _score_pairs(ec, pairs, op, C, graph_embedding, X, test_graph, train_graph)
     t0 = time.perf_counter()
     res = ranking.binary_ranking_scores(score, pairs['test'][2])
     rank_s = time.perf_counter() - t0
@@ -246,13 +257,16 @@ def evaluate_link_classification(train_graph, test_graph, X, op='hadamard', C=1.
                                  graph_embedding=None):
     """One run of the protocol for the embedding X (n, d) trained on train_graph: link_pairs(...) makes the pair sets, the classifier of `op`
     is fitted on the training pairs and the test pairs are ranked.  op: 'average', 'hadamard', 'l1', 'l2'; 'dot' (no fit); 'method'
-    (graph_embedding's own edge weight, through the evaluator's pair scores).  Returns a dict: 'auc', 'ap', the four pair counts, 'coef'
+    (graph_embedding's own edge weight, through the evaluator's pair scores); 'cn', 'jaccard', 'aa', 'ra', 'pa' (link_heuristics: the
+    neighbourhood score on train_graph, no fit, X is not consulted and may be None).  Returns a dict: 'auc', 'ap', the four pair counts, 'coef'
     ((d + 1,) weights then intercept, None without a fit), 'info' (EdgeClassifier.fit's), 'n_thresholds', and the seconds spent sampling,
     fitting, scoring and ranking."""
     _hip.require_device()
     t0 = time.perf_counter()
     pairs = link_pairs(train_graph, test_graph, seed, is_undirected, neg_ratio, max_train_pairs)
     sample_s = time.perf_counter() - t0
+    if op in HEURISTICS:
+        return _evaluate(None, pairs, op, C, graph_embedding, X, test_graph, sample_s, train_graph)
     X = np.asarray(X)
     if X.shape[0] != pairs['n']:
         raise ValueError('embedding has %d rows, the graphs %d nodes' % (X.shape[0], pairs['n']))
@@ -285,7 +299,8 @@ def evaluateStaticLinkClassification(digraph, graph_embedding, train_ratio=0.8, 
 def expLinkClassification(digraph, graph_embedding, rounds, ops=FEATURE_OPS, train_ratio=0.8, lcc=False, is_undirected=True, C=1.0, seed=0, neg_ratio=1.0,
                           max_train_pairs=None):
     """Every operator x round: {op: {'auc': [...], 'ap': [...]}}.  Round r seeds numpy's global stream with seed + r for the split, trains the
-    embedding once, builds the pair sets once (link_pairs(seed + r)) and keeps X on the device for all operators."""
+    embedding once, builds the pair sets once (link_pairs(seed + r)) and keeps X on the device for all operators.  `ops` may name neighbourhood
+    scores too -- ops=('hadamard', 'dot', 'cn', 'aa') is table 4 from one set of pairs."""
     _hip.require_device()
     out = {op: {'auc': [], 'ap': []} for op in ops}
     for r in range(rounds):
@@ -294,8 +309,13 @@ def expLinkClassification(digraph, graph_embedding, rounds, ops=FEATURE_OPS, tra
         t0 = time.perf_counter()
         pairs = link_pairs(train, test, seed + r, is_undirected, neg_ratio, max_train_pairs)
         sample_s = time.perf_counter() - t0
-        with EdgeClassifier(X) as ec:
-            for op in ops:
-                res = _evaluate(ec, pairs, op, C, graph_embedding, X, test, sample_s)
-                out[op]['auc'].append(res['auc']); out[op]['ap'].append(res['ap'])
+        ns = NeighbourScorer(train) if any(op in HEURISTICS for op in ops) else None          # the train graph is ingested once per round
+        try:
+            with EdgeClassifier(X) as ec:
+                for op in ops:
+                    res = _evaluate(ec, pairs, op, C, graph_embedding, X, test, sample_s, ns)
+                    out[op]['auc'].append(res['auc']); out[op]['ap'].append(res['ap'])
+        finally:
+            if ns is not None:
+                ns.close()
     return out

@@ -842,6 +842,46 @@ int gemhip_edgeclf_last_ms(gemhip_edgeclf_t h, double *out);
 int gemhip_edgeclf_info(gemhip_edgeclf_t h, int64_t *out);
 int gemhip_edgeclf_destroy(gemhip_edgeclf_t h);
 
+/* ------------------------------------------- link prediction baselines: neighbourhood scores of node pairs
+ * Replaces: networkx's common_neighbors, jaccard_coefficient, adamic_adar_index, resource_allocation_index and preferential_attachment, a
+ * Python loop per pair -- the first rows of node2vec's table 4.  All five are defined on the SIMPLE UNDIRECTED graph of the arc list: both
+ * orientations merged, self-loops dropped, repeated arcs merged, weights ignored.  G(u) the neighbour set, deg u = |G(u)|, I = G(u) & G(v):
+ *     cn |I| (int32)     jaccard |I| / (deg u + deg v - |I|), 0 for an empty union     aa sum_{w in I} 1 / ln(deg w)
+ *     ra sum_{w in I} 1 / deg w     pa deg u * deg v                                    (mask bits 1, 2, 4, 8, 16)
+ * cn is exact; jaccard is one correctly rounded fp64 division and pa one fp64 product, bit-equal to numpy's; aa and ra are fp64 sums of the
+ * entries of two tables the library makes on the host (1.0 / std::log((double)deg) and 1.0 / deg; 0 where deg < 2 and deg < 1), without
+ * atomics and in an order that is a function of the two lists alone: the same bytes on every run and for both orientations of a pair.
+ * Scheme: per pair the shorter list a is searched in the longer list b, element by element, by binary search (on equal lengths a is the
+ * list of the smaller id).  A pair with an empty a has no work item (all five scores are zero); a of at most CHUNK elements is one item, a
+ * longer one is cut into slices of CHUNK whose partial sums a second kernel adds in slice order.  Items of at most NARROW elements go to
+ * groups of 16 lanes, four per wavefront; the others to one wavefront each.
+ *
+ * gemhip_nbr_create: src / dst [m] (m >= 0), ingested on the host into a CSR (row_ptr int64, col int32 ascending per row) and uploaded once.
+ * n >= 1, every endpoint in [0, n) (GEMHIP_E_INVALID naming the first arc outside); n < 2^31 (GEMHIP_E_UNSUPPORTED).
+ * gemhip_nbr_degrees: deg_out [n].  gemhip_nbr_weights: w_out [n], which = 0 the aa table, 1 the ra table, read back from the device.
+ * gemhip_nbr_scores: st / ed [m], 1 <= m < 2^31 (GEMHIP_E_UNSUPPORTED above), ids in [0, n) and st != ed (GEMHIP_E_INVALID naming the first
+ * offending pair; networkx raises for st == ed at a degree-1 neighbour); repeated and adjacent pairs are legal.  Outputs [m] each, NULL where
+ * the score is not in mask.  Everything is checked on the host before any device call.
+ * gemhip_nbr_last_ms: out [6] = {ingest (host wall), graph upload (host wall), plan of the last call (host wall), its pair and item upload
+ * (host wall), its kernels (HIP events), its download (host wall)}.
+ * gemhip_nbr_info: out [12] = {n, stored neighbours, largest degree, lanes per narrow group, NARROW, CHUNK, then of the last call: narrow
+ * items, wide items, split pairs, partial slots, elements of the longest item, m}.  h == NULL: the constants only.
+ * Host only, working without a device: gemhip_nbr_graph_host (row_ptr_out [n + 1], col_out with room for 2 m entries, deg_out [n]: the ingest
+ * above), gemhip_nbr_weights_host (the two tables from given degrees) and gemhip_nbr_plan_host (counts_out [6] = {narrow items, wide items,
+ * split pairs, partial slots, elements of the longest item, pairs without an item}; deg [n] with entries in [0, n), pairs checked as above). */
+typedef struct gemhip_nbr *gemhip_nbr_t;
+int gemhip_nbr_create(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, gemhip_nbr_t *out);
+int gemhip_nbr_degrees(gemhip_nbr_t h, int32_t *deg_out);
+int gemhip_nbr_weights(gemhip_nbr_t h, int32_t which, double *w_out);
+int gemhip_nbr_scores(gemhip_nbr_t h, int64_t m, const int32_t *st, const int32_t *ed, int32_t mask, int32_t *cn_out, double *jaccard_out,
+                      double *aa_out, double *ra_out, double *pa_out);
+int gemhip_nbr_last_ms(gemhip_nbr_t h, double *out);
+int gemhip_nbr_info(gemhip_nbr_t h, int64_t *out);
+int gemhip_nbr_destroy(gemhip_nbr_t h);
+int gemhip_nbr_graph_host(int64_t n, int64_t m, const int32_t *src, const int32_t *dst, int64_t *row_ptr_out, int32_t *col_out, int32_t *deg_out);
+int gemhip_nbr_weights_host(int64_t n, const int32_t *deg, int32_t which, double *w_out);
+int gemhip_nbr_plan_host(int64_t n, const int32_t *deg, int64_t m, const int32_t *st, const int32_t *ed, int64_t *counts_out);
+
 #ifdef __cplusplus
 }
 #endif
