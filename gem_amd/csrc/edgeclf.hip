@@ -16,9 +16,9 @@
 //
 // Limits, refused on the host before any device call: d <= 255 and n, m < 2^31 (GEMHIP_E_UNSUPPORTED); |X| <= 1e18 (GEMHIP_E_INVALID: every
 // operator's result is then finite in fp32, which the solver requires of its matrix).
-#include "common.hpp"
+#include "eval_common.hpp"
 #include "nc_device.hpp"
-#include <chrono>
+#include <algorithm>
 #include <cmath>
 #include <memory>
 #include <vector>
@@ -31,7 +31,7 @@ struct gemhip_edgeclf {
     DevBuf<float> X, F;
     DevBuf<int32_t> st, ed;
     DevBuf<double> w, out;
-    EventMarks<2> watch;
+    Stopwatch watch;
     double ms[6] = {0, 0, 0, 0, 0, 0};                      // upload, features, scores, fit, the fit's mean pass, the fit's feature kernel
     int64_t passes = 0, loss_calls = 0, iterations = 0, last_m = 0;
 };
@@ -119,13 +119,7 @@ __global__ __launch_bounds__(EC_THREADS) void ec_scores_kernel(const float *__re
     }
 }
 
-double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-unsigned ec_grid(int64_t m)
-{
-    const int64_t g = (m + EC_PAIRS_PER_WG - 1) / EC_PAIRS_PER_WG;
-    return (unsigned)(g < 1 ? 1 : g < EC_MAX_GRID ? g : EC_MAX_GRID);
-}
+unsigned ec_grid(int64_t m) { return std::min<unsigned>(grid_of(m, EC_PAIRS_PER_WG), EC_MAX_GRID); }
 
 int check_pairs(const char *who, const gemhip_edgeclf *h, int op, bool op_matters, int64_t m, const int32_t *st, const int32_t *ed)
 {
@@ -134,9 +128,8 @@ int check_pairs(const char *who, const gemhip_edgeclf *h, int op, bool op_matter
     GEMHIP_REQUIRE(m >= 1, "%s: m = %lld pairs (need m >= 1)", who, (long long)m);
     if (m > INT32_MAX) return fail(GEMHIP_E_UNSUPPORTED, "%s: m = %lld: must be below 2^31", who, (long long)m);
     GEMHIP_REQUIRE(st && ed, "%s: NULL pair arrays", who);
-    for (int64_t p = 0; p < m; ++p)
-        GEMHIP_REQUIRE(st[p] >= 0 && st[p] < h->n && ed[p] >= 0 && ed[p] < h->n, "%s: pair %lld = (%d,%d) outside [0,%lld)", who, (long long)p, st[p], ed[p],
-                       (long long)h->n);
+    const int64_t bad = first_bad_pair(st, ed, m, h->n);
+    GEMHIP_REQUIRE(bad < 0, "%s: pair %lld = (%d,%d) outside [0,%lld)", who, (long long)bad, st[bad], ed[bad], (long long)h->n);
     return GEMHIP_OK;
 }
 
@@ -152,12 +145,10 @@ int upload_pairs(gemhip_edgeclf *h, int64_t m, const int32_t *st, const int32_t 
 int build_features(gemhip_edgeclf *h, int op, int64_t m, double *ms_out)
 {
     GEMHIP_CHECK(h->F.reserve((size_t)m * h->d));
-    GEMHIP_CHECK(h->watch.create());
-    GEMHIP_CHECK(h->watch.mark(0));
+    GEMHIP_CHECK(start(h->watch));
     hipLaunchKernelGGL(ec_features_kernel, dim3(ec_grid(m)), dim3(EC_THREADS), 0, 0, h->X.get(), h->ld, h->d, op, h->st.get(), h->ed.get(), m, h->F.get());
     GEMHIP_CHECK(hipGetLastError());
-    GEMHIP_CHECK(h->watch.mark(1));
-    GEMHIP_CHECK(h->watch.ms(0, 1, ms_out));
+    GEMHIP_CHECK(stop(h->watch, ms_out));
     return GEMHIP_OK;
 }
 
@@ -172,18 +163,16 @@ extern "C" int gemhip_edgeclf_create(int64_t n, int32_t d, int32_t ld, const flo
 {
     GEMHIP_REQUIRE(out != nullptr, "edgeclf_create: NULL output");
     *out = nullptr;
-    GEMHIP_REQUIRE(n >= 1, "edgeclf_create: n = %lld (need n >= 1)", (long long)n);
-    GEMHIP_REQUIRE(d >= 1 && ld >= d, "edgeclf_create: d = %d, ld = %d (need 1 <= d <= ld)", d, ld);
-    if (n > INT32_MAX) return fail(GEMHIP_E_UNSUPPORTED, "edgeclf_create: n = %lld: must be below 2^31", (long long)n);
-    if (d > EC_MAX_D) return fail(GEMHIP_E_UNSUPPORTED, "edgeclf_create: d = %d: at most %d (the solver's one LDS slab of padded rows)", d, EC_MAX_D);
-    GEMHIP_REQUIRE(X_host != nullptr, "edgeclf_create: NULL X");
-    for (int64_t i = 0; i < n; ++i)
-        for (int32_t c = 0; c < d; ++c) {
-            const float v = X_host[i * ld + c];
-            GEMHIP_REQUIRE(std::isfinite(v), "edgeclf_create: X[%lld][%d] is not finite", (long long)i, c);
-            GEMHIP_REQUIRE(std::fabs(v) <= EC_MAX_ABS, "edgeclf_create: |X[%lld][%d]| = %g above %g (a pair feature could overflow fp32)", (long long)i, c,
-                           (double)std::fabs(v), (double)EC_MAX_ABS);
-        }
+    const int rc = check_embedding("edgeclf_create", n, d, ld, X_host, 1, EC_MAX_D, "the solver's one LDS slab of padded rows");
+    if (rc) return rc;
+    const int64_t bad = first_bad_entry(X_host, n, d, ld, EC_MAX_ABS);
+    if (bad >= 0) {
+        const long long i = bad / d;
+        const int c = (int)(bad % d);
+        const float v = X_host[i * ld + c];
+        GEMHIP_REQUIRE(std::isfinite(v), "edgeclf_create: X[%lld][%d] is not finite", i, c);
+        return fail(GEMHIP_E_INVALID, "edgeclf_create: |X[%lld][%d]| = %g above %g (a pair feature could overflow fp32)", i, c, (double)std::fabs(v), (double)EC_MAX_ABS);
+    }
     std::unique_ptr<gemhip_edgeclf> h(new gemhip_edgeclf);
     h->n = n; h->ld = ld; h->d = d;
     const double t0 = wall_ms();
@@ -223,13 +212,11 @@ extern "C" int gemhip_edgeclf_scores(gemhip_edgeclf_t h, int32_t op, int64_t m, 
     if ((rc = upload_pairs(h, m, st, ed))) return rc;
     if (w) GEMHIP_CHECK(h->w.upload(w, (size_t)h->d + 1));
     GEMHIP_CHECK(h->out.reserve((size_t)m));
-    GEMHIP_CHECK(h->watch.create());
-    GEMHIP_CHECK(h->watch.mark(0));
+    GEMHIP_CHECK(start(h->watch));
     hipLaunchKernelGGL(ec_scores_kernel, dim3(ec_grid(m)), dim3(EC_THREADS), 0, 0, h->X.get(), h->ld, h->d, w ? op : 0, h->st.get(), h->ed.get(), m,
                        w ? h->w.get() : (const double *)nullptr, h->out.get());
     GEMHIP_CHECK(hipGetLastError());
-    GEMHIP_CHECK(h->watch.mark(1));
-    GEMHIP_CHECK(h->watch.ms(0, 1, &h->ms[2]));
+    GEMHIP_CHECK(stop(h->watch, &h->ms[2]));
     GEMHIP_CHECK(hipMemcpy(score_out, h->out, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
     return GEMHIP_OK;
 }

@@ -28,7 +28,7 @@
 //   gemhip_eval_topk       every sampled node's k best candidates, in the evaluator's order.
 // This file holds the kernels, the handle and the entry points; what the host computes around the launches (the CSR check, the mask's normal form,
 // the chunks, AP from the counts) is eval_host.hip, which needs no device.
-#include "common.hpp"
+#include "eval_common.hpp"
 #include "eval_host.hpp"
 #include <algorithm>
 #include <climits>
@@ -317,14 +317,12 @@ __global__ __launch_bounds__(EP_BLOCK) void eval_pairs_kernel(int da, int ld, co
 template <typename Launch>
 hipError_t timed_launch(double *ms, Launch launch)
 {
-    EventMarks<2> t;
-    hipError_t e = t.create();
+    Stopwatch t;
+    hipError_t e = start(t);
     if (e != hipSuccess) return e;
-    (void)t.mark(0);
     launch();
     e = hipGetLastError();
-    (void)t.mark(1);
-    return e != hipSuccess ? e : t.ms(0, 1, ms);
+    return e != hipSuccess ? e : stop(t, ms);
 }
 
 // The one map from a handle's (kind, da) to the kernels' compile-time <NV, KIND>: f(integral_constant NV, integral_constant KIND).
@@ -405,7 +403,8 @@ int ap_impl(gemhip_eval_t h, const char *who, bool masked, int32_t undirected, i
     GEMHIP_REQUIRE(h && nsample >= 0 && (nsample == 0 || (nodes && ap_out)), "%s: bad arguments", who);
     if (nsample == 0) return GEMHIP_OK;
     const int64_t n = h->n;
-    for (int64_t k = 0; k < nsample; ++k) GEMHIP_REQUIRE(nodes[k] >= 0 && nodes[k] < n, "%s: node %d outside [0,%lld)", who, nodes[k], (long long)n);
+    const int64_t bad = first_bad_index(nodes, nsample, n);
+    GEMHIP_REQUIRE(bad < 0, "%s: node %d outside [0,%lld)", who, nodes[bad], (long long)n);
     const bool use_mask = masked && h->has_mask;
     const ApChunks c = ap_chunks(h->row_ptr.data(), h->col.data(), use_mask ? h->mask.row_ptr.data() : nullptr, use_mask ? h->mask.col.data() : nullptr,
                                  undirected != 0, nsample, nodes);
@@ -474,7 +473,8 @@ extern "C" int gemhip_eval_topk(gemhip_eval_t h, int32_t undirected, int32_t use
     GEMHIP_REQUIRE(h->cols_sorted, "eval_topk: the edge lookup needs every CSR row's columns in ascending order");
     if (nsample == 0) return GEMHIP_OK;
     const int64_t n = h->n;
-    for (int64_t s = 0; s < nsample; ++s) GEMHIP_REQUIRE(nodes[s] >= 0 && nodes[s] < n, "eval_topk: node %d outside [0,%lld)", nodes[s], (long long)n);
+    const int64_t bad = first_bad_index(nodes, nsample, n);
+    GEMHIP_REQUIRE(bad < 0, "eval_topk: node %d outside [0,%lld)", nodes[bad], (long long)n);
     const bool masked = use_mask && h->has_mask;
     const int64_t *dmrp = masked ? h->d_mask_row_ptr.get() : nullptr; const int32_t *dmcol = masked ? h->d_mask_col.get() : nullptr;
     DevBuf<int32_t> dnodes, did; DevBuf<double> dscore; DevBuf<uint8_t> dhit;
@@ -543,7 +543,8 @@ extern "C" int gemhip_eval_sampled_ap(int64_t n, int32_t da, int32_t ld, const f
     GEMHIP_REQUIRE(n >= 1 && da >= 1 && da <= 512 && ld >= da && A_host && row_ptr && nsample >= 0 && (nsample == 0 || (nodes && ap_out)),
                    "eval_sampled_ap: bad arguments (da <= 512)");
     if (nsample == 0) return GEMHIP_OK;
-    for (int64_t k = 0; k < nsample; ++k) GEMHIP_REQUIRE(nodes[k] >= 0 && nodes[k] < n, "eval_sampled_ap: node %d outside [0,%lld)", nodes[k], (long long)n);
+    const int64_t bad = first_bad_index(nodes, nsample, n);
+    GEMHIP_REQUIRE(bad < 0, "eval_sampled_ap: node %d outside [0,%lld)", nodes[bad], (long long)n);
     gemhip_eval_t h = nullptr;
     int rc = gemhip_eval_create(n, da, ld, A_host, B_host, 0, row_ptr, col, &h);
     if (rc != GEMHIP_OK) return rc;

@@ -12,7 +12,7 @@
 //   km_slice_sum_kernel     the fp64 column sums of KM_SLICE consecutive members of one cluster, in a fixed shape.
 //   km_slice_reduce_kernel  a cluster's slices added in slice order.
 //   km_rowdist_kernel       |x_i - c_label(i)|^2 in the difference form, fp64: inertia, and the distances relocation ranks.
-//   km_sum_kernel           the sum of n doubles in a fixed shape.
+//   block_sum_f64_kernel    the sum of n doubles in a fixed shape (eval_common.hpp).
 //   km_seed_kernel          min(D2_i, |x_i - x_cand|^2) for up to KM_MAX_TRIALS candidate rows, fp32 difference form, and the fp64 sums of
 //                           every KM_SEED_BLOCK rows of it (a candidate's potential; the winner's are the next draw's cumulative blocks).
 //   km_gather_rows_kernel   rows of the padded matrix by id.
@@ -27,10 +27,9 @@
 //   K        <= KM_MAX_K = 16384     the (slab, cluster) histogram has at most KM_MAX_SLABS * K entries
 //   n_trials <= KM_MAX_TRIALS = 16   km_seed_kernel keeps the candidates' rows and a block's minima in LDS
 //   n        <  2^31                 row ids are int32
-#include "common.hpp"
+#include "eval_common.hpp"
 #include "kmeans_host.hpp"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <memory>
 #include <vector>
@@ -48,7 +47,7 @@ struct gemhip_kmeans {
     DevBuf<int32_t> labels, labels_old, hist, counts, tab, member, changed, cand, gather_idx, true_lab;
     DevBuf<double> dist, scalar, slice_part, sums, seed_part;
     DevBuf<unsigned long long> table;
-    EventMarks<2> watch;
+    Stopwatch watch;
     double ms[6] = {0, 0, 0, 0, 0, 0};                      // upload, seeding, fit, mean iteration, assign, update
     int64_t iterations = 0, relocations = 0;
 };
@@ -293,21 +292,6 @@ __global__ __launch_bounds__(256) void km_rowdist_kernel(const float *__restrict
     if (lane == 0) dist[i] = s;
 }
 
-// *out = sum of v[0 .. n): ONE workgroup; a thread's elements in index order, then a fixed tree.
-__global__ __launch_bounds__(KM_SUM_BLOCK) void km_sum_kernel(const double *__restrict__ v, int64_t n, double *__restrict__ out)
-{
-    __shared__ double s[KM_SUM_BLOCK];
-    double a = 0.0;
-    for (int64_t t = threadIdx.x; t < n; t += KM_SUM_BLOCK) a += v[t];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = KM_SUM_BLOCK / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = s[0];
-}
-
 // Workgroup b: rows [256 b, 256 b + 256), wavefront w rows w, w + 4, ...  For candidate t < T (row cand[t]):
 //     out_min[t][i] = min(D2[i], |x_i - x_cand|^2)    (D2 == nullptr: the distance itself), fp32, the difference form;
 //     part[t][b]    = the fp64 sum of the block's 256 values: lane l adds rows 4 l .. 4 l + 3 in order, then the butterfly.
@@ -375,9 +359,6 @@ __global__ __launch_bounds__(256) void km_contingency_kernel(const int32_t *__re
 }
 
 // ================================================================== host side
-unsigned km_grid(int64_t count, int per) { return (unsigned)((count + per - 1) / per < 1 ? 1 : (count + per - 1) / per); }
-double km_wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 int check_K(const char *who, const gemhip_kmeans *h, int32_t K)
 {
     GEMHIP_REQUIRE(h != nullptr, "%s: NULL handle", who);
@@ -411,7 +392,7 @@ int enqueue_assign(gemhip_kmeans *h, int32_t K, bool want_score)
 {
     GEMHIP_CHECK(h->labels.reserve((size_t)h->n));
     if (want_score) GEMHIP_CHECK(h->score.reserve((size_t)h->n));
-    hipLaunchKernelGGL(km_assign_kernel, dim3(km_grid(h->n, KM_ROWS)), dim3(KM_BLOCK), km_assign_lds(h->dpad), 0, h->Xp.get(), h->n, h->dpad, h->Cp.get(),
+    hipLaunchKernelGGL(km_assign_kernel, dim3(grid_of(h->n, KM_ROWS)), dim3(KM_BLOCK), km_assign_lds(h->dpad), 0, h->Xp.get(), h->n, h->dpad, h->Cp.get(),
                        h->cn.get(), (K + KM_CT - 1) / KM_CT, h->labels.get(), want_score ? h->score.get() : (float *)nullptr);
     GEMHIP_CHECK(hipGetLastError());
     h->K = K;
@@ -428,8 +409,8 @@ int run_update(gemhip_kmeans *h, int32_t K, std::vector<double> &sums, std::vect
     GEMHIP_CHECK(h->counts.reserve((size_t)K));
     GEMHIP_CHECK(h->member.reserve((size_t)n));
     GEMHIP_CHECK(hipMemsetAsync(h->hist, 0, (size_t)h->nslabs * K * sizeof(int32_t), 0));
-    hipLaunchKernelGGL(km_hist_kernel, dim3(km_grid(n, 256)), dim3(256), 0, 0, h->labels.get(), n, h->slab_rows, K, h->hist.get());
-    hipLaunchKernelGGL(km_slab_scan_kernel, dim3(km_grid(K, 4)), dim3(256), 0, 0, h->hist.get(), h->nslabs, K, h->counts.get());
+    hipLaunchKernelGGL(km_hist_kernel, dim3(grid_of(n, 256)), dim3(256), 0, 0, h->labels.get(), n, h->slab_rows, K, h->hist.get());
+    hipLaunchKernelGGL(km_slab_scan_kernel, dim3(grid_of(K, 4)), dim3(256), 0, 0, h->hist.get(), h->nslabs, K, h->counts.get());
     GEMHIP_CHECK(hipGetLastError());
     std::vector<int32_t> cnt((size_t)K);
     GEMHIP_CHECK(hipMemcpy(cnt.data(), h->counts, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -460,7 +441,7 @@ int run_update(gemhip_kmeans *h, int32_t K, std::vector<double> &sums, std::vect
     while (cw < dpad) cw *= 2;
     hipLaunchKernelGGL(km_fill_kernel, dim3((unsigned)h->nslabs), dim3(256), 0, 0, h->labels.get(), n, h->slab_rows, K, h->hist.get(), ptr, h->member.get());
     hipLaunchKernelGGL(km_slice_sum_kernel, dim3((unsigned)nslices), dim3(256), 0, 0, h->Xp.get(), dpad, cw, h->member.get(), d_begin, d_len, h->slice_part.get());
-    hipLaunchKernelGGL(km_slice_reduce_kernel, dim3(km_grid((int64_t)K * dpad, 256)), dim3(256), 0, 0, h->slice_part.get(), slice_ptr, K, dpad, h->sums.get());
+    hipLaunchKernelGGL(km_slice_reduce_kernel, dim3(grid_of((int64_t)K * dpad, 256)), dim3(256), 0, 0, h->slice_part.get(), slice_ptr, K, dpad, h->sums.get());
     GEMHIP_CHECK(hipGetLastError());
     sums.resize((size_t)K * dpad);
     GEMHIP_CHECK(hipMemcpy(sums.data(), h->sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -472,7 +453,7 @@ int run_update(gemhip_kmeans *h, int32_t K, std::vector<double> &sums, std::vect
 int enqueue_rowdist(gemhip_kmeans *h)
 {
     GEMHIP_CHECK(h->dist.reserve((size_t)h->n));
-    hipLaunchKernelGGL(km_rowdist_kernel, dim3(km_grid(h->n, 4)), dim3(256), 0, 0, h->Xp.get(), h->n, h->dpad, h->Cp.get(), h->labels.get(), h->dist.get());
+    hipLaunchKernelGGL(km_rowdist_kernel, dim3(grid_of(h->n, 4)), dim3(256), 0, 0, h->Xp.get(), h->n, h->dpad, h->Cp.get(), h->labels.get(), h->dist.get());
     GEMHIP_CHECK(hipGetLastError());
     return GEMHIP_OK;
 }
@@ -485,7 +466,7 @@ int gather_rows(gemhip_kmeans *h, const std::vector<int32_t> &idx, std::vector<f
     if (!m) return GEMHIP_OK;
     GEMHIP_CHECK(h->gather_idx.upload(idx.data(), idx.size()));
     GEMHIP_CHECK(h->rows_out.reserve(out.size()));
-    hipLaunchKernelGGL(km_gather_rows_kernel, dim3(km_grid(m * h->dpad, 256)), dim3(256), 0, 0, h->Xp.get(), h->dpad, h->gather_idx.get(), m, h->rows_out.get());
+    hipLaunchKernelGGL(km_gather_rows_kernel, dim3(grid_of(m * h->dpad, 256)), dim3(256), 0, 0, h->Xp.get(), h->dpad, h->gather_idx.get(), m, h->rows_out.get());
     GEMHIP_CHECK(hipGetLastError());
     GEMHIP_CHECK(hipMemcpy(out.data(), h->rows_out, out.size() * sizeof(float), hipMemcpyDeviceToHost));
     return GEMHIP_OK;
@@ -524,28 +505,23 @@ extern "C" int gemhip_kmeans_create(int64_t n, int32_t d, int32_t ld, const floa
 {
     GEMHIP_REQUIRE(out != nullptr, "kmeans_create: NULL output");
     *out = nullptr;
-    GEMHIP_REQUIRE(n >= 1, "kmeans_create: n = %lld (need n >= 1)", (long long)n);
-    GEMHIP_REQUIRE(d >= 1 && ld >= d, "kmeans_create: d = %d, ld = %d (need 1 <= d <= ld)", d, ld);
-    if (n > INT32_MAX) return fail(GEMHIP_E_UNSUPPORTED, "kmeans_create: n = %lld: must be below 2^31", (long long)n);
-    if (d > KM_MAX_D) return fail(GEMHIP_E_UNSUPPORTED, "kmeans_create: d = %d: at most %d (the LDS row tile of the assign kernel)", d, KM_MAX_D);
-    GEMHIP_REQUIRE(X_host != nullptr, "kmeans_create: NULL X");
-    const int64_t bad = km_first_nonfinite(X_host, n, d, ld);
+    const int rc = check_embedding("kmeans_create", n, d, ld, X_host, 1, KM_MAX_D, "the LDS row tile of the assign kernel");
+    if (rc) return rc;
+    const int64_t bad = first_bad_entry(X_host, n, d, ld, INFINITY);
     GEMHIP_REQUIRE(bad < 0, "kmeans_create: X[%lld][%d] is not finite", (long long)(bad / d), (int)(bad % d));
     std::unique_ptr<gemhip_kmeans> h(new gemhip_kmeans);
     h->n = n; h->ld = ld; h->d = d; h->dpad = (d + 7) & ~7;
     h->slab_rows = ((n + KM_MAX_SLABS - 1) / KM_MAX_SLABS + 255) / 256 * 256;
     h->nslabs = (n + h->slab_rows - 1) / h->slab_rows;
     h->mean_var = km_mean_variance(X_host, n, d, ld);
-    std::vector<float> xp((size_t)n * h->dpad, 0.f);
-    for (int64_t i = 0; i < n; ++i)
-        for (int32_t c = 0; c < d; ++c) xp[(size_t)i * h->dpad + c] = X_host[i * ld + c];
-    const double t0 = km_wall_ms();
+    std::vector<float> xp((size_t)n * h->dpad);
+    pad_rows(X_host, n, d, ld, h->dpad, xp.data());
+    const double t0 = wall_ms();
     GEMHIP_CHECK(h->Xp.upload(xp.data(), xp.size()));
     GEMHIP_CHECK(hipDeviceSynchronize());
-    h->ms[0] = km_wall_ms() - t0;
+    h->ms[0] = wall_ms() - t0;
     GEMHIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(km_assign_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)km_assign_lds(KM_MAX_D)));
-    GEMHIP_CHECK(h->watch.create());
     *out = h.release();
     return GEMHIP_OK;
 }
@@ -563,10 +539,9 @@ extern "C" int gemhip_kmeans_assign(gemhip_kmeans_t h, int32_t K, const float *c
     if ((rc = check_centres("kmeans_assign", K, h->d, centres))) return rc;
     GEMHIP_REQUIRE(labels_out != nullptr, "kmeans_assign: NULL output");
     if ((rc = upload_centres(h, K, centres))) return rc;
-    GEMHIP_CHECK(h->watch.mark(0));
+    GEMHIP_CHECK(start(h->watch));
     if ((rc = enqueue_assign(h, K, score_out_or_null != nullptr))) return rc;
-    GEMHIP_CHECK(h->watch.mark(1));
-    GEMHIP_CHECK(h->watch.ms(0, 1, &h->ms[4]));
+    GEMHIP_CHECK(stop(h->watch, &h->ms[4]));
     GEMHIP_CHECK(hipMemcpy(labels_out, h->labels, (size_t)h->n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (score_out_or_null) GEMHIP_CHECK(hipMemcpy(score_out_or_null, h->score, (size_t)h->n * sizeof(float), hipMemcpyDeviceToHost));
     return GEMHIP_OK;
@@ -577,17 +552,16 @@ extern "C" int gemhip_kmeans_update(gemhip_kmeans_t h, int32_t K, const int32_t 
     int rc = check_K("kmeans_update", h, K);
     if (rc) return rc;
     GEMHIP_REQUIRE(labels && centres_out && counts_out, "kmeans_update: NULL argument");
-    const int64_t bad = km_first_bad_label(labels, h->n, K);
+    const int64_t bad = first_bad_index(labels, h->n, K);
     GEMHIP_REQUIRE(bad < 0, "kmeans_update: label %lld = %d outside [0,%d)", (long long)bad, labels[bad], K);
     GEMHIP_CHECK(h->labels.upload(labels, (size_t)h->n));
     h->K = K;
     h->have_labels = true;
     std::vector<double> sums;
     std::vector<int64_t> counts;
-    GEMHIP_CHECK(h->watch.mark(0));
+    GEMHIP_CHECK(start(h->watch));
     if ((rc = run_update(h, K, sums, counts))) return rc;
-    GEMHIP_CHECK(h->watch.mark(1));
-    GEMHIP_CHECK(h->watch.ms(0, 1, &h->ms[5]));
+    GEMHIP_CHECK(stop(h->watch, &h->ms[5]));
     km_centres_from_sums(K, h->d, h->dpad, sums.data(), counts.data(), centres_out);
     for (int32_t k = 0; k < K; ++k) counts_out[k] = counts[k];
     return GEMHIP_OK;
@@ -613,12 +587,12 @@ extern "C" int gemhip_kmeans_fit(gemhip_kmeans_t h, int32_t K, float *centres_in
     bool strict = false;
     double shift = 0.0;
     h->iterations = 0; h->relocations = 0;
-    GEMHIP_CHECK(h->watch.mark(0));
+    GEMHIP_CHECK(start(h->watch));
     for (int it = 0; it < max_iter; ++it) {
         if ((rc = upload_centres(h, K, C.data()))) return rc;
         if ((rc = enqueue_assign(h, K, false))) return rc;
         GEMHIP_CHECK(hipMemsetAsync(h->changed, 0, sizeof(int32_t), 0));
-        hipLaunchKernelGGL(km_changed_kernel, dim3(km_grid(n, 256)), dim3(256), 0, 0, h->labels.get(), h->labels_old.get(), n, h->changed.get());
+        hipLaunchKernelGGL(km_changed_kernel, dim3(grid_of(n, 256)), dim3(256), 0, 0, h->labels.get(), h->labels_old.get(), n, h->changed.get());
         if ((rc = run_update(h, K, sums, counts))) return rc;
         int64_t moved = 0;
         if ((rc = relocate_empty(h, K, sums, counts, &moved))) return rc;
@@ -635,12 +609,11 @@ extern "C" int gemhip_kmeans_fit(gemhip_kmeans_t h, int32_t K, float *centres_in
     }
     if ((rc = upload_centres(h, K, C.data()))) return rc;
     if (!strict && (rc = enqueue_assign(h, K, false))) return rc;                   // labels that belong to the returned centres
-    GEMHIP_CHECK(h->watch.mark(1));
-    GEMHIP_CHECK(h->watch.ms(0, 1, &h->ms[2]));
+    GEMHIP_CHECK(stop(h->watch, &h->ms[2]));
     h->ms[3] = h->ms[2] / (double)h->iterations;
     if ((rc = enqueue_rowdist(h))) return rc;
     GEMHIP_CHECK(h->scalar.reserve(1));
-    hipLaunchKernelGGL(km_sum_kernel, dim3(1), dim3(KM_SUM_BLOCK), 0, 0, h->dist.get(), n, h->scalar.get());
+    hipLaunchKernelGGL((block_sum_f64_kernel<KM_SUM_BLOCK, gemhip_kmeans>), dim3(1), dim3(KM_SUM_BLOCK), 0, 0, h->dist.get(), n, h->scalar.get());
     GEMHIP_CHECK(hipGetLastError());
     double inertia = 0.0;
     GEMHIP_CHECK(hipMemcpy(&inertia, h->scalar, sizeof(double), hipMemcpyDeviceToHost));
@@ -663,7 +636,7 @@ extern "C" int gemhip_kmeans_seed_pp(gemhip_kmeans_t h, int32_t K, int32_t n_tri
     const int64_t badu = km_first_bad_uniform(u, (int64_t)K * n_trials);
     GEMHIP_REQUIRE(badu < 0, "kmeans_seed_pp: u[%lld][%d] = %g outside [0,1)", (long long)(badu / n_trials), (int)(badu % n_trials), u[badu]);
     const int64_t n = h->n, nb = (n + KM_SEED_BLOCK - 1) / KM_SEED_BLOCK;
-    const double t0 = km_wall_ms();
+    const double t0 = wall_ms();
     GEMHIP_CHECK(h->D2.reserve((size_t)n));
     GEMHIP_CHECK(h->cand_min.reserve((size_t)n * n_trials));
     GEMHIP_CHECK(h->seed_part.reserve((size_t)nb * n_trials));
@@ -711,7 +684,7 @@ extern "C" int gemhip_kmeans_seed_pp(gemhip_kmeans_t h, int32_t K, int32_t n_tri
         chosen_idx_out[k] = chosen[k];
         for (int c = 0; c < h->d; ++c) centres_out[(size_t)k * h->d + c] = rows[(size_t)k * h->dpad + c];
     }
-    h->ms[1] = km_wall_ms() - t0;
+    h->ms[1] = wall_ms() - t0;
     return GEMHIP_OK;
 }
 
@@ -722,13 +695,13 @@ extern "C" int gemhip_kmeans_contingency(gemhip_kmeans_t h, int32_t Kt, const in
     GEMHIP_REQUIRE(Kt >= 1, "kmeans_contingency: Kt = %d (need >= 1)", Kt);
     GEMHIP_REQUIRE(labels_true && table_out, "kmeans_contingency: NULL argument");
     if ((int64_t)h->K * Kt > KM_MAX_TABLE) return fail(GEMHIP_E_UNSUPPORTED, "kmeans_contingency: a %d x %d table: at most 2^26 entries", h->K, Kt);
-    const int64_t bad = km_first_bad_label(labels_true, h->n, Kt);
+    const int64_t bad = first_bad_index(labels_true, h->n, Kt);
     GEMHIP_REQUIRE(bad < 0, "kmeans_contingency: true label %lld = %d outside [0,%d)", (long long)bad, labels_true[bad], Kt);
     const size_t cells = (size_t)h->K * Kt;
     GEMHIP_CHECK(h->true_lab.upload(labels_true, (size_t)h->n));
     GEMHIP_CHECK(h->table.reserve(cells));
     GEMHIP_CHECK(hipMemsetAsync(h->table, 0, cells * sizeof(unsigned long long), 0));
-    hipLaunchKernelGGL(km_contingency_kernel, dim3(km_grid(h->n, 256)), dim3(256), 0, 0, h->labels.get(), h->true_lab.get(), h->n, Kt, h->table.get());
+    hipLaunchKernelGGL(km_contingency_kernel, dim3(grid_of(h->n, 256)), dim3(256), 0, 0, h->labels.get(), h->true_lab.get(), h->n, Kt, h->table.get());
     GEMHIP_CHECK(hipGetLastError());
     std::vector<unsigned long long> t(cells);
     GEMHIP_CHECK(hipMemcpy(t.data(), h->table, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost));

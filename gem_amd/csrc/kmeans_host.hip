@@ -6,21 +6,6 @@
 
 namespace gemhip {
 
-int64_t km_first_nonfinite(const float *X, int64_t n, int32_t d, int64_t ld)
-{
-    for (int64_t i = 0; i < n; ++i)
-        for (int32_t c = 0; c < d; ++c)
-            if (!std::isfinite(X[i * ld + c])) return i * d + c;
-    return -1;
-}
-
-int64_t km_first_bad_label(const int32_t *lab, int64_t n, int32_t K)
-{
-    for (int64_t t = 0; t < n; ++t)
-        if (lab[t] < 0 || lab[t] >= K) return t;
-    return -1;
-}
-
 int64_t km_first_bad_uniform(const double *u, int64_t count)
 {
     for (int64_t t = 0; t < count; ++t)

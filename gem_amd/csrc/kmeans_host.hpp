@@ -1,6 +1,7 @@
-// kmeans_host.hpp -- the host arithmetic of the k-means handle (kmeans_host.hip): the input checks, the padded centre block the assign kernel
-// reads, the centres of an update from its fp64 sums, sklearn's relocation of empty clusters with its order fixed, the bookkeeping of the
-// k-means++ draws, and the clustering scores (NMI, ARI, purity, homogeneity) of an integer contingency table.
+// kmeans_host.hpp -- the host arithmetic of the k-means handle (kmeans_host.hip): the check of the seeding's uniforms, the variance sklearn's
+// tol is relative to, the padded centre block the assign kernel reads, the centres of an update from its fp64 sums, sklearn's relocation of empty clusters with its order fixed, the bookkeeping of the
+// k-means++ draws, and the clustering scores (NMI, ARI, purity, homogeneity) of an integer contingency table.  The scans of the matrix and
+// of label lists, and the zero-padded copy of the matrix, are the ones every evaluation unit shares: matrix_host.hpp.
 // Plain C++, no HIP: everything here runs on a CPU (scripts/build_asan_kmeans.sh, tests/test_clustering.py); kmeans.hip words the refusals,
 // uploads and launches.
 #pragma once
@@ -9,10 +10,6 @@
 
 namespace gemhip {
 
-// The flat position i * d + c of the first X[i][c < d] that is not finite, or -1.  X [n][ld].
-int64_t km_first_nonfinite(const float *X, int64_t n, int32_t d, int64_t ld);
-// The first t with lab[t] outside [0, K), or -1.
-int64_t km_first_bad_label(const int32_t *lab, int64_t n, int32_t K);
 // The first t with u[t] outside [0, 1) (NaN included), or -1.
 int64_t km_first_bad_uniform(const double *u, int64_t count);
 // mean(var(X, axis=0)), fp64, two passes: what sklearn's tol is relative to.

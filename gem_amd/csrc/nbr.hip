@@ -17,9 +17,9 @@
 // gathered here; gemhip_nbr_weights reads them back from the device.
 //
 // Every refusal is decided on the host before any device call: nbr_host.hip finds the offender, this file words it.
-#include "common.hpp"
+#include "eval_common.hpp"
 #include "nbr_host.hpp"
-#include <chrono>
+#include <algorithm>
 #include <memory>
 #include <vector>
 
@@ -35,7 +35,7 @@ struct gemhip_nbr {
     DevBuf<double> jac, aa, ra, pa, part_aa, part_ra;
     DevBuf<NbrItem> narrow, wide;
     DevBuf<NbrSplit> split;
-    EventMarks<2> watch;
+    Stopwatch watch;
     double ms[6] = {0, 0, 0, 0, 0, 0};                       // ingest, graph upload, plan, pair and item upload, kernels, download
     int64_t last[6] = {0, 0, 0, 0, 0, 0};                    // of the last call: narrow items, wide items, split pairs, slots, longest item, m
 };
@@ -131,13 +131,7 @@ __global__ __launch_bounds__(NBR_THREADS) void nbr_finish_kernel(const int32_t *
     }
 }
 
-double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-unsigned nbr_grid(int64_t units, int64_t per_block)
-{
-    const int64_t g = (units + per_block - 1) / per_block;
-    return (unsigned)(g < 1 ? 1 : g < NBR_MAX_GRID ? g : NBR_MAX_GRID);
-}
+unsigned nbr_grid(int64_t units, int64_t per_block) { return std::min<unsigned>(grid_of(units, per_block), NBR_MAX_GRID); }
 
 int check_graph(const char *who, int64_t n, int64_t m, const int32_t *src, const int32_t *dst)
 {
@@ -145,7 +139,7 @@ int check_graph(const char *who, int64_t n, int64_t m, const int32_t *src, const
     if (n > INT32_MAX) return fail(GEMHIP_E_UNSUPPORTED, "%s: n = %lld: must be below 2^31", who, (long long)n);
     GEMHIP_REQUIRE(m >= 0, "%s: m = %lld arcs (need m >= 0)", who, (long long)m);
     GEMHIP_REQUIRE(m == 0 || (src && dst), "%s: NULL arc arrays", who);
-    const int64_t bad = nbr_first_bad_arc(n, m, src, dst);
+    const int64_t bad = first_bad_pair(src, dst, m, n);
     GEMHIP_REQUIRE(bad < 0, "%s: arc %lld = (%d,%d) outside [0,%lld)", who, (long long)bad, src[bad], dst[bad], (long long)n);
     return GEMHIP_OK;
 }
@@ -287,8 +281,7 @@ extern "C" int gemhip_nbr_scores(gemhip_nbr_t h, int64_t m, const int32_t *st, c
     GEMHIP_CHECK(hipDeviceSynchronize());
     h->ms[3] = wall_ms() - t0;
 
-    GEMHIP_CHECK(h->watch.create());
-    GEMHIP_CHECK(h->watch.mark(0));
+    GEMHIP_CHECK(start(h->watch));
     GEMHIP_CHECK(hipMemsetAsync(h->cn, 0, (size_t)m * sizeof(int32_t), 0));          // a pair without an item: all five scores are zero
     for (double *p : {h->jac.get(), h->aa.get(), h->ra.get(), h->pa.get()}) GEMHIP_CHECK(hipMemsetAsync(p, 0, (size_t)m * sizeof(double), 0));
     if (n_narrow) {
@@ -308,8 +301,7 @@ extern "C" int gemhip_nbr_scores(gemhip_nbr_t h, int64_t m, const int32_t *st, c
                            n_split, h->part_cn.get(), h->part_aa.get(), h->part_ra.get(), h->cn.get(), h->jac.get(), h->aa.get(), h->ra.get(), h->pa.get());
         GEMHIP_CHECK(hipGetLastError());
     }
-    GEMHIP_CHECK(h->watch.mark(1));
-    GEMHIP_CHECK(h->watch.ms(0, 1, &h->ms[4]));
+    GEMHIP_CHECK(stop(h->watch, &h->ms[4]));
 
     t0 = wall_ms();
     if (mask & NBR_CN) GEMHIP_CHECK(hipMemcpy(cn_out, h->cn, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));

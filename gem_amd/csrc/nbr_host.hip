@@ -6,13 +6,6 @@
 
 namespace gemhip {
 
-int64_t nbr_first_bad_arc(int64_t n, int64_t m, const int32_t *src, const int32_t *dst)
-{
-    for (int64_t e = 0; e < m; ++e)
-        if (src[e] < 0 || src[e] >= n || dst[e] < 0 || dst[e] >= n) return e;
-    return -1;
-}
-
 int64_t nbr_first_bad_pair(int64_t n, int64_t m, const int32_t *st, const int32_t *ed, bool *self_pair)
 {
     for (int64_t p = 0; p < m; ++p) {

@@ -50,8 +50,6 @@ struct NbrPlan {
     int64_t empty = 0;                 // pairs with la == 0: no item
 };
 
-// The first arc with an endpoint outside [0, n), or -1.
-int64_t nbr_first_bad_arc(int64_t n, int64_t m, const int32_t *src, const int32_t *dst);
 // The first pair with an id outside [0, n) (*self_pair = false) or with st == ed (*self_pair = true), or -1.
 int64_t nbr_first_bad_pair(int64_t n, int64_t m, const int32_t *st, const int32_t *ed, bool *self_pair);
 

@@ -26,11 +26,10 @@
 //   d  <= NC_MAX_D = 255    one thread per padded column of x~ and one LDS sub-slab of 64 x 256 floats
 //   K  <= NC_MAX_K = 65536  the top-k kernel walks a row's K logits once per predicted label
 //   n  <  2^31              row ids are int32; a row list (n_train, m) is below 2^31 too
-#include "common.hpp"
+#include "eval_common.hpp"
 #include "nc_device.hpp"
 #include "nc_host.hpp"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <limits>
 #include <memory>
@@ -51,7 +50,7 @@ struct gemhip_nc {
     DevBuf<double> d_W, d_Wblk, partF, partG, partH, outF, outG, outH, d_scores;
     DevBuf<uint8_t> d_pred;
     DevBuf<unsigned long long> d_counts;
-    EventMarks<2> watch;
+    Stopwatch watch;
     double ms[4] = {0, 0, 0, 0};                            // upload, fit, mean pass, predict
     int64_t passes = 0, loss_calls = 0, iterations = 0;
 };
@@ -321,15 +320,13 @@ __global__ void nc_topk_kernel(const double *__restrict__ scores, int64_t rows, 
 }
 
 // ================================================================== host side
-unsigned grid_of(int64_t count, int per) { return (unsigned)((count + per - 1) / per < 1 ? 1 : (count + per - 1) / per); }
-double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 int check_rows(const char *who, const gemhip_nc *h, int64_t m, const int32_t *idx)
 {
     GEMHIP_REQUIRE(m >= 1, "%s: %lld rows (need >= 1)", who, (long long)m);
     GEMHIP_REQUIRE(idx != nullptr, "%s: NULL row list", who);
     if (m > INT32_MAX) return fail(GEMHIP_E_UNSUPPORTED, "%s: %lld rows: must be below 2^31", who, (long long)m);
-    for (int64_t t = 0; t < m; ++t) GEMHIP_REQUIRE(idx[t] >= 0 && idx[t] < h->n, "%s: row %lld = %d outside [0,%lld)", who, (long long)t, idx[t], (long long)h->n);
+    const int64_t bad = first_bad_index(idx, m, h->n);
+    GEMHIP_REQUIRE(bad < 0, "%s: row %lld = %d outside [0,%lld)", who, (long long)bad, idx[bad], (long long)h->n);
     return GEMHIP_OK;
 }
 
@@ -439,21 +436,17 @@ extern "C" int gemhip_nc_create(int64_t n, int32_t d, int32_t ld, const float *X
 {
     GEMHIP_REQUIRE(out != nullptr, "nc_create: NULL output");
     *out = nullptr;
-    GEMHIP_REQUIRE(n >= 1, "nc_create: n = %lld (need n >= 1)", (long long)n);
-    GEMHIP_REQUIRE(d >= 1 && ld >= d, "nc_create: d = %d, ld = %d (need 1 <= d <= ld)", d, ld);
-    if (n > INT32_MAX) return fail(GEMHIP_E_UNSUPPORTED, "nc_create: n = %lld: must be below 2^31", (long long)n);
-    if (d > NC_MAX_D) return fail(GEMHIP_E_UNSUPPORTED, "nc_create: d = %d: at most %d (one LDS slab of the padded rows)", d, NC_MAX_D);
-    GEMHIP_REQUIRE(X_host != nullptr, "nc_create: NULL X");
-    for (int64_t i = 0; i < n; ++i)
-        for (int32_t c = 0; c < d; ++c) GEMHIP_REQUIRE(std::isfinite(X_host[i * ld + c]), "nc_create: X[%lld][%d] is not finite", (long long)i, c);
+    int rc = check_embedding("nc_create", n, d, ld, X_host, 1, NC_MAX_D, "one LDS slab of the padded rows");
+    if (rc) return rc;
+    const int64_t bad = first_bad_entry(X_host, n, d, ld, INFINITY);
+    GEMHIP_REQUIRE(bad < 0, "nc_create: X[%lld][%d] is not finite", (long long)(bad / d), (int)(bad % d));
     std::unique_ptr<gemhip_nc> h(new gemhip_nc);
     h->n = n; h->ld = ld; h->d = d; h->d1 = d + 1; h->dp = (d + 1 + 31) & ~31;
     const double t0 = wall_ms();
     GEMHIP_CHECK(h->X.upload(X_host, (size_t)n * ld));
     GEMHIP_CHECK(hipDeviceSynchronize());
     h->ms[0] = wall_ms() - t0;
-    const int rc = set_lds_limit(h->dp);
-    if (rc) return rc;
+    if ((rc = set_lds_limit(h->dp))) return rc;
     *out = h.release();
     return GEMHIP_OK;
 }
@@ -463,11 +456,8 @@ int gemhip::nc_create_from_device(int64_t n, int32_t d, int64_t ld, const float 
 {
     GEMHIP_REQUIRE(out != nullptr, "nc_create_from_device: NULL output");
     *out = nullptr;
-    GEMHIP_REQUIRE(n >= 1, "nc_create_from_device: n = %lld (need n >= 1)", (long long)n);
-    GEMHIP_REQUIRE(d >= 1 && ld >= d, "nc_create_from_device: d = %d, ld = %lld (need 1 <= d <= ld)", d, (long long)ld);
-    if (n > INT32_MAX) return fail(GEMHIP_E_UNSUPPORTED, "nc_create_from_device: n = %lld: must be below 2^31", (long long)n);
-    if (d > NC_MAX_D) return fail(GEMHIP_E_UNSUPPORTED, "nc_create_from_device: d = %d: at most %d (one LDS slab of the padded rows)", d, NC_MAX_D);
-    GEMHIP_REQUIRE(X_dev != nullptr, "nc_create_from_device: NULL X");
+    int rc = check_embedding("nc_create_from_device", n, d, ld, X_dev, 1, NC_MAX_D, "one LDS slab of the padded rows");
+    if (rc) return rc;
     std::unique_ptr<gemhip_nc> h(new gemhip_nc);
     h->n = n; h->ld = ld; h->d = d; h->d1 = d + 1; h->dp = (d + 1 + 31) & ~31;
     const double t0 = wall_ms();
@@ -475,8 +465,7 @@ int gemhip::nc_create_from_device(int64_t n, int32_t d, int64_t ld, const float 
     GEMHIP_CHECK(hipMemcpy(h->X, X_dev, (size_t)n * ld * sizeof(float), hipMemcpyDeviceToDevice));
     GEMHIP_CHECK(hipDeviceSynchronize());
     h->ms[0] = wall_ms() - t0;
-    const int rc = set_lds_limit(h->dp);
-    if (rc) return rc;
+    if ((rc = set_lds_limit(h->dp))) return rc;
     *out = h.release();
     return GEMHIP_OK;
 }
@@ -678,8 +667,7 @@ extern "C" int gemhip_nc_predict_topk(gemhip_nc_t h, int64_t m, const int32_t *i
     GEMHIP_CHECK(h->d_pred.reserve((size_t)chunk * K));
     GEMHIP_CHECK(h->d_counts.reserve((size_t)3 * K + 1));
     GEMHIP_CHECK(hipMemsetAsync(h->d_counts, 0, ((size_t)3 * K + 1) * sizeof(unsigned long long), 0));
-    GEMHIP_CHECK(h->watch.create());
-    GEMHIP_CHECK(h->watch.mark(0));
+    GEMHIP_CHECK(start(h->watch));
     for (int64_t first = 0; first < m; first += chunk) {
         const int64_t rows = first + chunk < m ? chunk : m - first;
         enqueue_scores(h, first, rows);
@@ -688,8 +676,7 @@ extern "C" int gemhip_nc_predict_topk(gemhip_nc_t h, int64_t m, const int32_t *i
         GEMHIP_CHECK(hipGetLastError());
         if (pred_or_null) GEMHIP_CHECK(hipMemcpy(pred_or_null + (size_t)first * K, h->d_pred, (size_t)rows * K, hipMemcpyDeviceToHost));
     }
-    GEMHIP_CHECK(h->watch.mark(1));
-    GEMHIP_CHECK(h->watch.ms(0, 1, &h->ms[3]));
+    GEMHIP_CHECK(stop(h->watch, &h->ms[3]));
     std::vector<unsigned long long> cnt((size_t)3 * K + 1);
     GEMHIP_CHECK(hipMemcpy(cnt.data(), h->d_counts, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (size_t q = 0; q < (size_t)3 * K; ++q) counts_out[q] = (int64_t)cnt[q];

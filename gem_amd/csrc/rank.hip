@@ -22,7 +22,7 @@
 //
 // Device memory: 2 x 12 bytes per key for the two key / payload buffers, 8 for the scan, 1 for the labels, m / 2 for the tile table.
 // Limits: 1 <= m < 2^31 (positions are int32; GEMHIP_E_INVALID below, GEMHIP_E_UNSUPPORTED above), refused on the host before any launch.
-#include "common.hpp"
+#include "eval_common.hpp"
 #include "rank_host.hpp"
 #include <algorithm>
 #include <vector>
@@ -326,7 +326,6 @@ __global__ __launch_bounds__(SC_THREADS) void rank_final_kernel(const long long 
 }
 
 // ================================================================== host side
-unsigned blocks_of(int64_t count, int per) { return (unsigned)((count + per - 1) / per < 1 ? 1 : (count + per - 1) / per); }
 
 struct RankWork {
     DevBuf<uint64_t> kA, kB, packed, tile, bsum;
@@ -337,7 +336,7 @@ struct RankWork {
     DevBuf<long long> partU, outU;
     uint64_t *keys = nullptr;            // the sorted keys and their positions: kA / vA or kB / vB
     int32_t *perm = nullptr;
-    EventMarks<2> watch;
+    Stopwatch watch;
 };
 
 struct RankLast {
@@ -375,8 +374,7 @@ int check_labels(const char *who, int64_t m, const uint8_t *label, int64_t *P_ou
 // with a wait, which the readback or allocation that follows would make anyway.
 int begin_stretch(RankWork &w)
 {
-    GEMHIP_CHECK(w.watch.create());
-    GEMHIP_CHECK(w.watch.mark(0));
+    GEMHIP_CHECK(start(w.watch));
     return GEMHIP_OK;
 }
 
@@ -384,8 +382,7 @@ int end_stretch(RankWork &w)
 {
     double ms = 0.0;
     GEMHIP_CHECK(hipGetLastError());
-    GEMHIP_CHECK(w.watch.mark(1));
-    GEMHIP_CHECK(w.watch.ms(0, 1, &ms));
+    GEMHIP_CHECK(stop(w.watch, &ms));
     last().ms += ms;
     return GEMHIP_OK;
 }
@@ -420,7 +417,7 @@ int sort_scores(RankWork &w, int64_t m, const double *score)
     int rc = begin_stretch(w);
     if (rc) return rc;
     GEMHIP_CHECK(hipMemsetAsync(w.hist, 0, sizeof(uint32_t) * RANK_PASSES * RANK_BUCKETS, 0));
-    const unsigned wide = blocks_of(m, RK_THREADS) < 2048u ? blocks_of(m, RK_THREADS) : 2048u;
+    const unsigned wide = grid_of(m, RK_THREADS) < 2048u ? grid_of(m, RK_THREADS) : 2048u;
     hipLaunchKernelGGL(rank_keys_kernel, dim3(wide), dim3(RK_THREADS), 0, 0, w.kA.get(), w.vA.get(), m);
     hipLaunchKernelGGL(rank_digit_hist_kernel, dim3(wide), dim3(RK_THREADS), 0, 0, w.kA.get(), m, w.hist.get());
     GEMHIP_CHECK(hipGetLastError());
@@ -452,7 +449,7 @@ int group_table(RankWork &w, int64_t m, const uint8_t *label, int64_t *T_out)
     GEMHIP_CHECK(w.packed.reserve((size_t)m));
     int rc = begin_stretch(w);
     if (rc) return rc;
-    hipLaunchKernelGGL(rank_flags_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, 0, w.keys, w.perm, w.label.get(), m, w.packed.get());
+    hipLaunchKernelGGL(rank_flags_kernel, dim3(grid_of(m, 256)), dim3(256), 0, 0, w.keys, w.perm, w.label.get(), m, w.packed.get());
     if ((rc = scan_in_place(w, w.packed, m, true))) return rc;
     if ((rc = end_stretch(w))) return rc;
     uint64_t tail = 0;
@@ -463,7 +460,7 @@ int group_table(RankWork &w, int64_t m, const uint8_t *label, int64_t *T_out)
     GEMHIP_CHECK(w.gfp.reserve((size_t)T));
     GEMHIP_CHECK(w.thr.reserve((size_t)T));
     if ((rc = begin_stretch(w))) return rc;
-    hipLaunchKernelGGL(rank_groups_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, 0, w.keys, w.packed.get(), m, T, w.gtp.get(), w.gfp.get(), w.thr.get());
+    hipLaunchKernelGGL(rank_groups_kernel, dim3(grid_of(m, 256)), dim3(256), 0, 0, w.keys, w.packed.get(), m, T, w.gtp.get(), w.gfp.get(), w.thr.get());
     *T_out = T;
     last().T = T;
     return end_stretch(w);

@@ -13,7 +13,7 @@
 // One iteration (gemhip_tsne_run):
 //   tsne_repulse_kernel      exact sum_j w^2 (y_i - y_j) and sum_j w, w = 1 / (1 + |y_i - y_j|^2): rows in registers, tiles of y_j in LDS read as
 //                            broadcasts, j split across the grid in slices
-//   tsne_reduce_rep_kernel   the slices' partials in slice order (fp64);  tsne_sum_kernel: Z = sum of the rows' sums, one workgroup, fixed order
+//   tsne_reduce_rep_kernel   the slices' partials in slice order (fp64);  block_sum_f64_kernel (eval_common.hpp): Z = sum of the rows' sums, one workgroup, fixed order
 //   tsne_attract_kernel      one wavefront per row: the sparse sums over the row's own list and over the transposed arcs that are not mutual,
 //                            KL over the same nonzeros, grad = 4 (exaggeration * attr - rep / Z)
 //   tsne_update_kernel       sklearn's _gradient_descent step (gains, momentum)
@@ -22,7 +22,7 @@
 // order that depends on scheduling, tsne_sort_rows sorts by a key that is unique inside a row.  Every floating-point sum has a fixed shape: a
 // thread's own elements in index order, then a butterfly over the wavefront (a + b == b + a, so every lane holds the same bits), slices and
 // slabs in index order.  The k smallest keys of a row are a set: the order in which tsne_knn_kernel meets the candidates does not change it.
-#include "common.hpp"
+#include "eval_common.hpp"
 #include <cmath>
 #include <memory>
 
@@ -421,21 +421,6 @@ __global__ __launch_bounds__(256) void tsne_reduce_rep_kernel(const double *__re
     rep[i] = x; rep[n + i] = y; zrow[i] = z - 1.0;
 }
 
-// *out = sum of v[0 .. n): ONE workgroup; a thread's elements in index order, then a fixed tree.
-__global__ __launch_bounds__(SUM_BLOCK) void tsne_sum_kernel(const double *__restrict__ v, int64_t n, double *__restrict__ out)
-{
-    __shared__ double s[SUM_BLOCK];
-    double a = 0.0;
-    for (int64_t t = threadIdx.x; t < n; t += SUM_BLOCK) a += v[t];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = SUM_BLOCK / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = s[0];
-}
-
 // One nonzero P_ij of row i: attr += P w (y_i - y_j), kl += P log(max(P, eps) / max(w / Z, eps)).  fp64 (the sums are short).
 __device__ __forceinline__ void attract_term(double P, float2 yi, float2 yj, double Z, bool want_kl, double &ax, double &ay, double &kl)
 {
@@ -513,23 +498,13 @@ __global__ __launch_bounds__(256) void tsne_reset_kernel(int64_t n, float2 *__re
 }
 
 // ================================================================== host side
-unsigned grid_of(int64_t count, int per) { return (unsigned)((count + per - 1) / per < 1 ? 1 : (count + per - 1) / per); }
-
-using Stopwatch = EventMarks<2>;                        // start and stop marks on the null stream, made on first use
-hipError_t start(Stopwatch &w) { const hipError_t e = w.create(); return e != hipSuccess ? e : w.mark(0); }
-hipError_t stop(Stopwatch &w, double *ms) { const hipError_t e = w.mark(1); return e != hipSuccess ? e : w.ms(0, 1, ms); }      // waits for the stream
-
 int check_matrix(const char *who, int64_t n, int32_t d, int32_t ld, const float *X)
 {
-    GEMHIP_REQUIRE(n >= 2, "%s: n = %lld (need n >= 2)", who, (long long)n);
-    GEMHIP_REQUIRE(d >= 1 && ld >= d, "%s: d = %d, ld = %d (need 1 <= d <= ld)", who, d, ld);
-    GEMHIP_REQUIRE(X != nullptr, "%s: NULL X", who);
-    if (n > INT32_MAX) return fail(GEMHIP_E_UNSUPPORTED, "%s: n = %lld: must be below 2^31", who, (long long)n);
-    for (int64_t i = 0; i < n; ++i)
-        for (int32_t c = 0; c < d; ++c) {
-            const float v = X[i * ld + c];
-            GEMHIP_REQUIRE(std::isfinite(v) && std::fabs(v) <= 1e15f, "%s: X[%lld][%d] = %g is not finite or above 1e15 in magnitude", who, (long long)i, c, (double)v);
-        }
+    const int rc = check_embedding(who, n, d, ld, X, 2, 0, nullptr);
+    if (rc) return rc;
+    const int64_t bad = first_bad_entry(X, n, d, ld, 1e15f);
+    GEMHIP_REQUIRE(bad < 0, "%s: X[%lld][%d] = %g is not finite or above 1e15 in magnitude", who, (long long)(bad / d), (int)(bad % d),
+                   (double)X[bad / d * ld + bad % d]);
     return GEMHIP_OK;
 }
 
@@ -619,10 +594,10 @@ int enqueue_gradient(gemhip_tsne *h, double exaggeration, bool want_kl)
     const int64_t n = h->n;
     hipLaunchKernelGGL(tsne_repulse_kernel, dim3(grid_of(n, REP_ROWS), (unsigned)h->nslices), dim3(REP_BLOCK), 0, 0, h->Y.get(), n, h->jslice, h->part.get());
     hipLaunchKernelGGL(tsne_reduce_rep_kernel, dim3(grid_of(n, 256)), dim3(256), 0, 0, h->part.get(), n, h->nslices, h->rep.get(), h->zrow.get());
-    hipLaunchKernelGGL(tsne_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, 0, h->zrow.get(), n, h->scal.get());
+    hipLaunchKernelGGL((block_sum_f64_kernel<SUM_BLOCK, gemhip_tsne>), dim3(1), dim3(SUM_BLOCK), 0, 0, h->zrow.get(), n, h->scal.get());
     hipLaunchKernelGGL(tsne_attract_kernel, dim3(grid_of(n, 4)), dim3(256), 0, 0, h->Y.get(), n, h->k, h->id.get(), h->p.get(), h->f_pt.get(), h->t_ptr.get(),
                        h->t_src.get(), h->t_p.get(), h->t_mut.get(), h->rep.get(), h->scal.get(), exaggeration, want_kl ? 1 : 0, h->grad.get(), h->klrow.get());
-    if (want_kl) hipLaunchKernelGGL(tsne_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, 0, h->klrow.get(), n, h->scal.get() + 1);
+    if (want_kl) hipLaunchKernelGGL((block_sum_f64_kernel<SUM_BLOCK, gemhip_tsne>), dim3(1), dim3(SUM_BLOCK), 0, 0, h->klrow.get(), n, h->scal.get() + 1);
     GEMHIP_CHECK(hipGetLastError());
     return GEMHIP_OK;
 }
@@ -742,7 +717,7 @@ extern "C" int gemhip_tsne_run(gemhip_tsne_t h, int32_t n_iter, double exaggerat
         hipLaunchKernelGGL(tsne_update_kernel, dim3(grid_of(n, 256)), dim3(256), 0, 0, n, h->grad.get(), h->upd.get(), h->gains.get(), h->Y.get(), (float)momentum,
                            (float)lr, h->gnrow.get());
     }
-    hipLaunchKernelGGL(tsne_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, 0, h->gnrow.get(), n, h->scal.get() + 2);
+    hipLaunchKernelGGL((block_sum_f64_kernel<SUM_BLOCK, gemhip_tsne>), dim3(1), dim3(SUM_BLOCK), 0, 0, h->gnrow.get(), n, h->scal.get() + 2);
     GEMHIP_CHECK(hipGetLastError());
     GEMHIP_CHECK(stop(h->watch, &h->ms[3]));
     double s[3];

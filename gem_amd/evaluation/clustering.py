@@ -12,6 +12,7 @@ import warnings
 import numpy as np
 
 from gem_amd import _hip
+from gem_amd.evaluation._handle import DeviceHandle, embedding_matrix
 
 TOL = 1e-4
 MAX_ITER = 300
@@ -47,30 +48,16 @@ def l2_normalize(X):
     return (X / np.where(norm > 0, norm, 1.0)[:, None]).astype(np.float32)
 
 
-class KMeans(object):
+class KMeans(DeviceHandle):
     """gemhip_kmeans_t with its calls; X is uploaded once: `with KMeans(X) as km:`."""
+
+    _destroy = 'gemhip_kmeans_destroy'
 
     def __init__(self, X, d=None):
         """X (n, ld) float32; d: how many leading columns count (all by default; the rest is padding the device never reads)."""
-        _hip.require_device()
-        X = _hip.as_f32(X)
-        if X.ndim != 2:
-            raise ValueError('X must be (n, d)')
-        self.n = X.shape[0]
-        self.d = X.shape[1] if d is None else int(d)
-        self._h = ct.c_void_p()
-        _hip.check(_hip.lib().gemhip_kmeans_create(self.n, self.d, X.shape[1], _hip.ptr(X, ct.c_float), ct.byref(self._h)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._h:
-            _hip.lib().gemhip_kmeans_destroy(self._h)
-            self._h = ct.c_void_p()
+        DeviceHandle.__init__(self)
+        X, self.n, self.d, ld = embedding_matrix(X, d)
+        _hip.check(_hip.lib().gemhip_kmeans_create(self.n, self.d, ld, _hip.ptr(X, ct.c_float), ct.byref(self._h)))
 
     def _centres(self, K, centres):
         C = np.array(centres, dtype=np.float32, order='C')

@@ -12,6 +12,7 @@ import warnings
 import numpy as np
 
 from gem_amd import _hip
+from gem_amd.evaluation._handle import DeviceHandle, embedding_matrix
 from gem_amd.evaluation import ranking
 from gem_amd.evaluation.link_heuristics import HEURISTICS, NeighbourScorer
 from gem_amd.evaluation.node_classification import DEC_TOL, MAX_ITER
@@ -121,30 +122,16 @@ def link_pairs(train_graph, test_graph, seed=0, is_undirected=True, neg_ratio=1.
             'n_train_pos': len(ptr_st), 'n_train_neg': len(ntr_st), 'n_test_pos': len(pte_st), 'n_test_neg': len(nte_st)}
 
 
-class EdgeClassifier(object):
+class EdgeClassifier(DeviceHandle):
     """gemhip_edgeclf_t with its calls; X is uploaded once: `with EdgeClassifier(X) as ec:`."""
+
+    _destroy = 'gemhip_edgeclf_destroy'
 
     def __init__(self, X, d=None):
         """X (n, ld) float32; d: how many leading columns count (all by default; the rest is padding the device never reads)."""
-        _hip.require_device()
-        X = _hip.as_f32(X)
-        if X.ndim != 2:
-            raise ValueError('X must be (n, d)')
-        self.n = X.shape[0]
-        self.d = X.shape[1] if d is None else int(d)
-        self._h = ct.c_void_p()
-        _hip.check(_hip.lib().gemhip_edgeclf_create(self.n, self.d, X.shape[1], _hip.ptr(X, ct.c_float), ct.byref(self._h)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._h:
-            _hip.lib().gemhip_edgeclf_destroy(self._h)
-            self._h = ct.c_void_p()
+        DeviceHandle.__init__(self)
+        X, self.n, self.d, ld = embedding_matrix(X, d)
+        _hip.check(_hip.lib().gemhip_edgeclf_create(self.n, self.d, ld, _hip.ptr(X, ct.c_float), ct.byref(self._h)))
 
     @staticmethod
     def _pairs(st, ed):

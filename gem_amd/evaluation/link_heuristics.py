@@ -11,6 +11,7 @@ import numpy as np
 
 from gem_amd import _hip
 from gem_amd.evaluation import ranking
+from gem_amd.evaluation._handle import DeviceHandle
 
 HEURISTICS = ('cn', 'jaccard', 'aa', 'ra', 'pa')
 _BIT = {'cn': 1, 'jaccard': 2, 'aa': 4, 'ra': 8, 'pa': 16}
@@ -34,29 +35,19 @@ def constants():
     return {'lanes_per_narrow_group': int(out[3]), 'narrow': int(out[4]), 'chunk': int(out[5])}
 
 
-class NeighbourScorer(object):
+class NeighbourScorer(DeviceHandle):
     """gemhip_nbr_t with its calls; the graph is ingested and uploaded once: `with NeighbourScorer(graph) as ns:`."""
+
+    _destroy = 'gemhip_nbr_destroy'
 
     def __init__(self, graph):
         """graph: anything gem_amd.graph.edge_arrays accepts (an nx graph with node ids 0 .. n-1, an EdgeListGraph)."""
         from gem_amd.graph import edge_arrays
-        _hip.require_device()
+        DeviceHandle.__init__(self)
         n, src, dst, _, _ = edge_arrays(graph)
         src = _hip.as_i32(src); dst = _hip.as_i32(dst)
         self.n = int(n)
-        self._h = ct.c_void_p()
         _hip.check(_hip.lib().gemhip_nbr_create(self.n, len(src), _hip.ptr(src, ct.c_int32), _hip.ptr(dst, ct.c_int32), ct.byref(self._h)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._h:
-            _hip.lib().gemhip_nbr_destroy(self._h)
-            self._h = ct.c_void_p()
 
     def degrees(self):
         """int32 (n,): the degrees in the simple undirected graph."""

@@ -12,6 +12,7 @@ import warnings
 import numpy as np
 
 from gem_amd import _hip
+from gem_amd.evaluation._handle import DeviceHandle, embedding_matrix
 
 DEC_TOL = 1e-10                 # a class is converged after the step whose Newton decrement is at most DEC_TOL * max(1, F)
 MAX_ITER = 50
@@ -71,31 +72,17 @@ def f1_from_counts(tp, fp, fn):
     return micro, float(per_class.mean()) if len(per_class) else 0.0
 
 
-class NodeClassifier(object):
+class NodeClassifier(DeviceHandle):
     """gemhip_nc_t with its calls; X is uploaded once: `with NodeClassifier(X) as nc:`."""
+
+    _destroy = 'gemhip_nc_destroy'
 
     def __init__(self, X, d=None):
         """X (n, ld) float32; d: how many leading columns count (all by default; the rest is padding the device never reads)."""
-        _hip.require_device()
-        X = _hip.as_f32(X)
-        if X.ndim != 2:
-            raise ValueError('X must be (n, d)')
-        self.n = X.shape[0]
-        self.d = X.shape[1] if d is None else int(d)
+        DeviceHandle.__init__(self)
+        X, self.n, self.d, ld = embedding_matrix(X, d)
         self.K = 0
-        self._h = ct.c_void_p()
-        _hip.check(_hip.lib().gemhip_nc_create(self.n, self.d, X.shape[1], _hip.ptr(X, ct.c_float), ct.byref(self._h)))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._h:
-            _hip.lib().gemhip_nc_destroy(self._h)
-            self._h = ct.c_void_p()
+        _hip.check(_hip.lib().gemhip_nc_create(self.n, self.d, ld, _hip.ptr(X, ct.c_float), ct.byref(self._h)))
 
     def set_labels(self, Y):
         """Y as label_csr takes it, or a (K, row_ptr, cls) triple."""

@@ -22,6 +22,8 @@ evaluate_reconstruction_gpu returns the reference's whole tuple (MAP, prec_curv,
 """
 import numpy as np
 
+from gem_amd.evaluation._handle import DeviceHandle
+
 
 def _adjacency_bool(digraph, n):
     A = np.zeros((n, n), dtype=bool)
@@ -251,8 +253,10 @@ def _score_operands(graph_embedding, X):
                               '-- use evaluateStaticGraphReconstruction' % name)
 
 
-class _DeviceEvaluator(object):
+class _DeviceEvaluator(DeviceHandle):
     """gemhip_eval_* handle: embedding and CSR (columns sorted) of the true graph on the device, uploaded once."""
+
+    _destroy = 'gemhip_eval_destroy'
 
     def __init__(self, n, src, dst, graph_embedding, X):
         import ctypes as C
@@ -263,9 +267,8 @@ class _DeviceEvaluator(object):
         if A.shape[0] != n:
             raise ValueError('embedding has %d rows, the graph %d nodes' % (A.shape[0], n))
         row_ptr, col, _ = to_csr(n, src, dst, None, sort_cols=True)
-        _hip.require_device()
+        DeviceHandle.__init__(self)
         self.n = n
-        self._h = C.c_void_p()
         _hip.check(_hip.lib().gemhip_eval_create(n, A.shape[1], A.shape[1], _hip.ptr(A, C.c_float), _hip.ptr(B, C.c_float), kind,
                                                  _hip.ptr(row_ptr, C.c_int64), _hip.ptr(col, C.c_int32), C.byref(self._h)))
 
@@ -322,17 +325,6 @@ class _DeviceEvaluator(object):
         ms = self._C.c_double(0.0)
         self._hip.check(self._hip.lib().gemhip_eval_last_pairs_ms(self._h, self._C.byref(ms)))
         return ms.value
-
-    def close(self):
-        if self._h:
-            self._hip.lib().gemhip_eval_destroy(self._h)
-            self._h = self._C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def sampled_ap_gpu(graph, graph_embedding, X, nodes, is_undirected=True):

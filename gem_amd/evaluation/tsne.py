@@ -11,6 +11,7 @@ import time
 import numpy as np
 
 from gem_amd import _hip
+from gem_amd.evaluation._handle import DeviceHandle, embedding_matrix
 
 EXPLORATION_ITER = 250                  # sklearn TSNE._EXPLORATION_MAX_ITER
 N_ITER_CHECK = 50                       # sklearn TSNE._N_ITER_CHECK
@@ -45,31 +46,18 @@ def learning_rate_auto(n, early_exaggeration):
     return max(n / early_exaggeration / 4.0, 50.0)
 
 
-class TsneHandle(object):
+class TsneHandle(DeviceHandle):
     """gemhip_tsne_t with its calls; `with TsneHandle(X, perplexity) as h:`."""
 
+    _destroy = 'gemhip_tsne_destroy'
+
     def __init__(self, X, perplexity):
-        _hip.require_device()
-        X = _hip.as_f32(X)
-        if X.ndim != 2:
-            raise ValueError('X must be (n, d)')
-        self.n, self.d = X.shape
-        self._h = C.c_void_p()
+        DeviceHandle.__init__(self)
+        X, self.n, self.d, _ = embedding_matrix(X)
         _hip.check(_hip.lib().gemhip_tsne_create(self.n, self.d, self.d, _hip.ptr(X, C.c_float), float(perplexity), C.byref(self._h)))
         info = (C.c_int64 * 4)()
         _hip.check(_hip.lib().gemhip_tsne_info(self._h, info))
         self.k, self.n_slices = int(info[2]), int(info[3])
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if self._h:
-            _hip.lib().gemhip_tsne_destroy(self._h)
-            self._h = C.c_void_p()
 
     def set_embedding(self, Y):
         Y = _hip.as_f32(Y)

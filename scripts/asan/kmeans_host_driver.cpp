@@ -1,6 +1,7 @@
-// Stand-alone driver of gem_amd/csrc/kmeans_host.hip for scripts/build_asan_kmeans.sh: every host function on small built cases, the results
-// checked against values worked out by hand.  Plain C++, its own main; prints one summary line, exits non-zero on a wrong value.
+// Stand-alone driver of gem_amd/csrc/kmeans_host.hip (and of the matrix_host.hip scans k-means ingests with) for scripts/build_asan_kmeans.sh:
+// every host function on small built cases, the results checked against values worked out by hand.  Plain C++, its own main; prints one summary line, exits non-zero on a wrong value.
 #include "../../gem_amd/csrc/kmeans_host.hpp"
+#include "../../gem_amd/csrc/matrix_host.hpp"
 #include <cmath>
 #include <cstdio>
 #include <limits>
@@ -21,11 +22,11 @@ int main()
         const int64_t n = 5; const int d = 3; const int64_t ld = 4;
         std::vector<float> X((size_t)n * ld, 1.f);
         for (int64_t i = 0; i < n; ++i) X[i * ld + 3] = std::numeric_limits<float>::quiet_NaN();          // padding: never read
-        EXPECT(km_first_nonfinite(X.data(), n, d, ld) == -1);
+        EXPECT(first_bad_entry(X.data(), n, d, ld, INFINITY) == -1);
         X[3 * ld + 2] = std::numeric_limits<float>::infinity();
-        EXPECT(km_first_nonfinite(X.data(), n, d, ld) == 3 * d + 2);
+        EXPECT(first_bad_entry(X.data(), n, d, ld, INFINITY) == 3 * d + 2);
         const int32_t lab[4] = {0, 2, 3, -1};
-        EXPECT(km_first_bad_label(lab, 2, 3) == -1 && km_first_bad_label(lab, 4, 3) == 2 && km_first_bad_label(lab, 4, 4) == 3);
+        EXPECT(first_bad_index(lab, 2, 3) == -1 && first_bad_index(lab, 4, 3) == 2 && first_bad_index(lab, 4, 4) == 3);
         const double u[4] = {0.0, 0.999, 1.0, std::numeric_limits<double>::quiet_NaN()};
         EXPECT(km_first_bad_uniform(u, 2) == -1 && km_first_bad_uniform(u, 4) == 2 && km_first_bad_uniform(u + 3, 1) == 0);
         const float V[6] = {1.f, 10.f, 3.f, 10.f, 5.f, 10.f};                                              // columns (1, 3, 5) and (10, 10, 10)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# AddressSanitizer + UBSan run of k-means' host half (gem_amd/csrc/kmeans_host.hip: input checks, centre block, centres from sums, relocation
+# AddressSanitizer + UBSan run of k-means' host half (gem_amd/csrc/kmeans_host.hip and the shared scans of matrix_host.hip: input checks, centre block, centres from sums, relocation
 # of empty clusters, k-means++ draw bookkeeping, NMI / ARI / purity) as a stand-alone program with its own main
 # (scripts/asan/kmeans_host_driver.cpp), in the manner of build_asan_nc.sh.  Plain C++, no HIP, runs on a CPU; nothing sanitized is loaded
 # into python and nothing runs on a GPU.
@@ -10,7 +10,7 @@ cd "$(dirname "$0")/.."
 OUT=gem_amd/build/asan_kmeans
 mkdir -p $OUT
 CL=/opt/rocm/lib/llvm/bin/clang++
-$CL -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer gem_amd/csrc/kmeans_host.hip scripts/asan/kmeans_host_driver.cpp -o $OUT/kmeans_host_asan
+$CL -x c++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer gem_amd/csrc/kmeans_host.hip gem_amd/csrc/matrix_host.hip scripts/asan/kmeans_host_driver.cpp -o $OUT/kmeans_host_asan
 ASAN_OPTIONS="halt_on_error=0" UBSAN_OPTIONS="print_stacktrace=1" timeout 300 $OUT/kmeans_host_asan > $OUT/out.txt 2> $OUT/err.txt || { cat $OUT/out.txt; tail -30 $OUT/err.txt; echo "driver failed"; exit 1; }
 cat $OUT/out.txt
 echo "sanitizer reports: $(grep -c 'ERROR: AddressSanitizer\|ERROR: LeakSanitizer\|runtime error:' $OUT/err.txt || true)"
